@@ -10,15 +10,21 @@ arithmetic; the build-defined RGB spatial-conv branch is timed be
 (`rgb_branch`: its kernels alone, and the whole north-star step WITH it, skeleton + IMU + RGB as
 one step), its parity unpinned.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--graph]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--graph] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value,
+ms_per_step, dtype, config, step_mfma). `--full` adds every other leg described below, each a run
+of its own after the timed steps. `--dump-outputs DIR` writes what the last timed step computed
+(loss, logits, flat gradient, updated flat parameters; the inputs and initial weights are seeded,
+so two builds can be compared output for output) as DIR/<name>.npy.
 
 `bench.py --gpus N` without a torch.distributed environment starts the N ranks itself (one per
 GPU, torch.distributed.run as a child process) and fails if the node has fewer than N GPUs.
 
 Prints ONE JSON line (rank 0) with value = global clips/s over the timed region (max over
 ranks) in the parity-meeting bf16x3 mode (split-bf16 products on bf16 MFMA, fp32 activations: logits
-within 1e-3 of the fp64 oracle, identical argmax), the roofline of the dominant kernel (the
+within 1e-3 of the fp64 oracle, identical argmax) and, with --full, the roofline of the dominant kernel (the
 temporal-conv input-gradient clip-window GEMM, measured live with HIP events on the stream it runs on;
 HBM traffic from profiles/r06_roofline_pmc.json) and the CPU baseline (the oracle timed on this host's
 cores on a bounded sample). The bf16 and fp32 modes' step times are reported beside it
@@ -71,6 +77,13 @@ def parse():
                         "musa: the root main.py's musa_model")
     p.add_argument("--no-targcn", action="store_true", help="skip the config-2 TARGCN and config-5 lines in the default run")
     p.add_argument("--cpu-seconds", type=float, default=24.0)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every other leg (rooflines, the other precision modes, eval "
+                        "forward, phased backward, autograd path, sensor / loader / RGB legs, the cfg 2 / cfg 5 / musa "
+                        "models, the CPU baseline) and add their keys to the line; off: the headline figure only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed (loss, logits, the flat "
+                        "gradient and the updated flat parameters) as DIR/<name>.npy, float32")
     p.add_argument("--launch-check", action="store_true",
                    help="start the --gpus N ranks exactly as a bench run does, all-reduce each rank's id over gloo and "
                         "print the ranks seen; touches no GPU (tests/test_bench_launch.py)")
@@ -112,6 +125,29 @@ def launch_check(world, rank):
         print(json.dumps({"launch_check": True, "world": dist.get_world_size(),
                           "ranks_seen": [int(i) - 1 for i in ids.tolist()]}), flush=True)
     dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, step, model):
+    """--dump-outputs: what a caller of the timed step holds after its last call, as float32
+    <name>.npy files: the returned loss, the logits (step.out), the flat gradient (step.grads, what
+    the parameters' .grad attributes view) and the updated flat parameters. An array that would take
+    the total past DUMP_BYTES is cut to a fixed seeded sample of its elements, in index order
+    (np.random.default_rng(0).choice(n, k, replace=False), sorted), the same from run to run."""
+    os.makedirs(path, exist_ok=True)
+    if step.out.is_cuda:
+        torch.cuda.synchronize()
+    arrays = {"loss": step.loss, "logits": step.out, "grads": step.grads, "params": model.flat_parameters()}
+    left = DUMP_BYTES
+    for i, (name, t) in enumerate(arrays.items()):
+        x = t.detach().to(torch.float32).cpu().numpy()
+        share = (left // (len(arrays) - i) - 128) // 4  # elements this array may take of what is left
+        if x.size > share:
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x))
+        left -= x.nbytes + 128  # + the .npy header
 
 
 ROOFLINE_PMC = os.path.join(ROOT, "profiles", "r06_roofline_pmc.json")
@@ -578,7 +614,7 @@ def replica_seconds(fn, steps, warmup):
     return dt / steps, world
 
 
-def targcn_bench(dev, B=256, V=17, steps=10, warmup=3, precision="bf16", cpu_seconds=0.0):
+def targcn_bench(dev, B=256, V=17, steps=10, warmup=3, precision="bf16", cpu_seconds=0.0, full=True, dump=None):
     """BASELINE config 2: skeleton-only TARGCN (TRAGCN.py:177-224, V=17 joints, T=30, bf16 GEMM
     operands) training step (fwd + CE + bwd + RMSprop) at B=256 on one GPU, synthetic clips,
     random-init weights. ms_per_step is the whole step; the recurrence is 2 layers x 30 dependent
@@ -590,13 +626,17 @@ def targcn_bench(dev, B=256, V=17, steps=10, warmup=3, precision="bf16", cpu_sec
     step = f3.TargcnStep(model, B, lr=1e-5)
     x, y = torch.from_numpy(src).to(dev), torch.from_numpy(lab).to(dev)
     dt, world = replica_seconds(lambda: step(x, y), steps, warmup)
-    stages = targcn_stage_times(model, step, x, y, B, V, precision)
+    if dump:
+        dump_outputs(dump, step, model)
+    stages = targcn_stage_times(model, step, x, y, B, V, precision) if full else None
     rec = {"metric": "clips/sec (fwd+bwd) TARGCN skeleton-only, B=256, 1 GPU", "value": round(world * B / dt, 1),
            "unit": "clips/s", "n_gpus": world, "scaling": "weak", "ms_per_step": round(dt * 1e3, 3),
            "dtype": precision, "steps": steps,
            "config": {"workload": f"targcn_V{V}_T30_B{B}", "global_batch": world * B, "joints": V, "frames": 30,
                       "gru_layers": 2, "hidden": 64, "ta_layers": 2, "parallelism": f"replicas{world}"},
            "final_loss": round(float(step.loss.item()), 5), "stages": stages}
+    if not full:
+        del rec["stages"]
     if cpu_seconds > 0:  # the oracle (pinned bit-exactly to the reference) on this host's cores
         threads = cpu_threads()
         torch.set_num_threads(threads)
@@ -654,7 +694,7 @@ def targcn_stage_times(model, step, x, y, B, V, precision, reps=5):
     return out
 
 
-def sktr_bench(dev, B=256, steps=10, warmup=3, cpu_seconds=0.0, precision="bf16"):
+def sktr_bench(dev, B=256, steps=10, warmup=3, cpu_seconds=0.0, precision="bf16", full=True, dump=None):
     """BASELINE config 5: SkeletonTransformer(3, 14, 30, 11, 32, 6, 16, 8) training step (fwd + CE +
     bwd + RMSprop, train-mode FFN dropout and stochastic depth) at B=256 on one GPU, synthetic clips,
     random-init weights. precision "bf16" (BASELINE cfg 5): the block Linears on bf16 MFMA, fp32
@@ -689,8 +729,10 @@ def sktr_bench(dev, B=256, steps=10, warmup=3, cpu_seconds=0.0, precision="bf16"
         step(xb[i], yb[i])
 
     dt, world = replica_seconds(fold_step, steps, warmup)
+    if dump:
+        dump_outputs(dump, step, model)
     fp32_ms = None
-    if precision != "fp32":  # the parity mode's step time beside it
+    if full and precision != "fp32":  # the parity mode's step time beside it
         m32 = f3.SkeletonTransformer(device=dev)
         s32 = f3.SktrStep(m32, B)
         fp32_ms = round(replica_seconds(lambda: s32(xd, yd), steps, warmup)[0] * 1e3, 3)
@@ -719,7 +761,7 @@ def sktr_bench(dev, B=256, steps=10, warmup=3, cpu_seconds=0.0, precision="bf16"
     return rec
 
 
-def musa_bench(dev, B=256, steps=10, warmup=3, cpu_seconds=0.0, precision="bf16"):
+def musa_bench(dev, B=256, steps=10, warmup=3, cpu_seconds=0.0, precision="bf16", full=True, dump=None):
     """The model the root Multimodal_Fall3/main.py trains (musa_model.Model, main.py:307-320: 14 joints,
     30 frames, two streams, DropBlocks, RMSprop) — training step (fwd + CE + bwd + RMSprop) at B=256 on
     one GPU, fp32, synthetic clips; plus the HBM roofline of its depthwise temporal Conv1D."""
@@ -732,8 +774,10 @@ def musa_bench(dev, B=256, steps=10, warmup=3, cpu_seconds=0.0, precision="bf16"
     step = f3.musa.MusaStep(model, B)
     xd, yd = torch.from_numpy(x).to(dev), torch.from_numpy(lab).to(dev)
     dt, world = replica_seconds(lambda: step(xd, yd), steps, warmup)
+    if dump:
+        dump_outputs(dump, step, model)
     fp32_ms = None
-    if precision != "fp32":  # the parity mode's step time beside it
+    if full and precision != "fp32":  # the parity mode's step time beside it
         m32 = f3.musa.Model(11, 14, 300, f3.musa.adjGraph("coco_cut", "uniform"), True, True, 41, device=dev)
         s32 = f3.musa.MusaStep(m32, B)
         fp32_ms = round(replica_seconds(lambda: s32(xd, yd), steps, warmup)[0] * 1e3, 3)
@@ -744,7 +788,7 @@ def musa_bench(dev, B=256, steps=10, warmup=3, cpu_seconds=0.0, precision="bf16"
            "steps": steps, "config": {"workload": f"musa_V14_T30_B{B}", "global_batch": world * B, "joints": 14,
                                       "frames": 30, "dropblock": True, "parallelism": f"replicas{world}"},
            "final_loss": round(float(step.loss.item()), 5), "fp32_mode_ms_per_step": fp32_ms}
-    if dist.is_available() and dist.is_initialized() and dist.get_rank() != 0:
+    if not full or (dist.is_available() and dist.is_initialized() and dist.get_rank() != 0):
         return rec
     # depthwise temporal conv roofline (SepTemporal_Block depth_conv, C=128, V=14, T=30, B clips):
     # algorithmic bytes = x + y (+ w, b); the BatchNorm sums are fused in the epilogue
@@ -830,6 +874,13 @@ def loader_bench(model, dev, B=256, V=18, S=6, C=11, n=20480):
 REFERENCE_CPU = {"value": 77.4, "unit": "clips/s", "cores": 8, "kind": "reference",
                  "sample": "reference TwoStreamSTGCAN_BiLSTM (HAR V=14, S=15, 11 classes) fwd+bwd+RMSprop at B=256, "
                            "torch CPU fp32, 3.308 s/step, timed in the survey container (BASELINE.md 2a)"}
+
+
+# keys of the result line that take runs of their own: present only with --full
+FULL_KEYS = ("roofline", "roofline_wgrad_l1", "roofline_wgrad_l5", "roofline_wgrad_l6", "roofline_wgrad_kernel",
+             "roofline_tcn_fwd", "roofline_graph_mix", "roofline_gcn", "sensor", "loader", "eval_forward",
+             "dp_phased_backward", "main_py_autograd_path", "cfg2_targcn", "cfg5_sktr", "musa_model", "rgb_branch",
+             "fp32_mode", "bf16_mode", "cpu_baseline")
 
 
 MODE_NOTES = {
@@ -975,7 +1026,7 @@ def model_leg(model, a):
     process after the 3-stream, fp32-mode and roofline legs, the TARGCN step read 8.4 ms against 6.7 ms
     alone (profiles/r03_bench.json vs r03_bench_tg_alone.json)."""
     cmd = [sys.executable, os.path.abspath(__file__), "--model", model, "--steps", "10", "--warmup", "3",
-           "--precision", "bf16"]
+           "--precision", "bf16", "--full"]
     if a.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
@@ -1010,21 +1061,23 @@ def main():
     import fall_multimodal_amd as f3
     from oracle.prng import synthetic_batch
 
+    leg_cpu = 6.0 if (a.full and not a.no_cpu_baseline and world == 1) else 0.0
+    leg_dump = a.dump_outputs if rank == 0 else None
     if a.model == "targcn":
-        rec = targcn_bench(dev, steps=a.steps, warmup=a.warmup, precision=a.precision,
-                           cpu_seconds=0.0 if (a.no_cpu_baseline or world > 1) else 6.0)
+        rec = targcn_bench(dev, steps=a.steps, warmup=a.warmup, precision=a.precision, cpu_seconds=leg_cpu,
+                           full=a.full, dump=leg_dump)
         if rank == 0:
             print(json.dumps(rec), flush=True)
         return
     if a.model == "musa":
-        rec = musa_bench(dev, steps=a.steps, warmup=a.warmup, cpu_seconds=0.0 if (a.no_cpu_baseline or world > 1) else 6.0,
-                         precision=a.precision)
+        rec = musa_bench(dev, steps=a.steps, warmup=a.warmup, cpu_seconds=leg_cpu, precision=a.precision, full=a.full,
+                         dump=leg_dump)
         if rank == 0:
             print(json.dumps(rec), flush=True)
         return
     if a.model == "sktr":
-        rec = sktr_bench(dev, steps=a.steps, warmup=a.warmup, cpu_seconds=0.0 if (a.no_cpu_baseline or world > 1) else 6.0,
-                         precision=a.precision)
+        rec = sktr_bench(dev, steps=a.steps, warmup=a.warmup, cpu_seconds=leg_cpu, precision=a.precision, full=a.full,
+                         dump=leg_dump)
         if rank == 0:
             print(json.dumps(rec), flush=True)
         return
@@ -1056,8 +1109,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss = float(step.loss.item())
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, step, model)
     phased = None
-    if world == 1 and rank == 0:  # the data-parallel two-phase backward's own cost, measured on one GPU
+    if a.full and world == 1 and rank == 0:  # the data-parallel two-phase backward's own cost, measured on one GPU
         step.phased = True
         for _ in range(2):
             step(sk, se, lb)
@@ -1071,24 +1126,26 @@ def main():
         phased = {"ms_per_step": round(pm, 3), "vs_phase0": round(pm / (dt / a.steps * 1e3), 4),
                   "note": "backward as phase 1 (head, sensor, layers 4-6) + phase 2 (layers 0-3), the DP path "
                           "without the collective; phase 0 = the one-pass backward the N=1 value uses"}
-    one = rank == 0 and world == 1
+    one = a.full and rank == 0 and world == 1
+    lead = a.full and rank == 0
     fp32m = fp32_mode_bench(dev, a, V, S, C, sk, se, lb) if (one and a.precision != "fp32") else None
     bf16m = fp32_mode_bench(dev, a, V, S, C, sk, se, lb, precision="bf16") if (one and a.precision == "bf16x3") else None
-    ev = eval_throughput(model, sk, se) if rank == 0 else None
-    agp = autograd_path_bench(model, sk, se, lb, steps=a.steps) if (rank == 0 and world == 1) else None
-    roofs = roofline_kernels(dev, B, V, a.precision) if rank == 0 else None
-    legs = rank == 0 and world == 1 and not a.no_targcn
+    ev = eval_throughput(model, sk, se) if lead else None
+    agp = autograd_path_bench(model, sk, se, lb, steps=a.steps) if one else None
+    roofs = roofline_kernels(dev, B, V, a.precision) if lead else None
+    legs = one and not a.no_targcn
     tgrec = model_leg("targcn", a) if legs else None
     skrec = model_leg("sktr", a) if legs else None
     murec = model_leg("musa", a) if legs else None
-    mix = mix_roofline(dev, B, V, a.precision) if rank == 0 else None
-    sens = sensor_bench(dev) if (rank == 0 and world == 1) else None
-    rgbr = rgb_bench(dev) if (rank == 0 and world == 1 and not a.no_targcn) else None
+    mix = mix_roofline(dev, B, V, a.precision) if lead else None
+    sens = sensor_bench(dev) if one else None
+    rgbr = rgb_bench(dev) if legs else None
     if rgbr is not None:
         rgbr["north_star_step_with_rgb"] = rgb_step_bench(dev, a, V, S, C, sk, se, lb)
-    ldr = loader_bench(model, dev, B, V, S, C) if (rank == 0 and world == 1 and not a.no_targcn) else None
+    ldr = loader_bench(model, dev, B, V, S, C) if legs else None
     if rank == 0:
-        cpu = None if a.no_cpu_baseline or world > 1 else cpu_baseline(a.layout, V, S, a.cpu_seconds)
+        cpu = None if (not a.full or a.no_cpu_baseline or world > 1) else cpu_baseline(a.layout, V, S, a.cpu_seconds)
+        roofs = roofs or {}
         rec = {
             "metric": "clips/sec (fwd+bwd) 3-stream Fall3, B=256, 1/2/4/8 GPUs; top-1 acc parity",
             "value": round(world * B * a.steps / dt, 2),
@@ -1108,15 +1165,15 @@ def main():
             "data": "synthetic",
             "config": {"workload": f"fall3_3stream_{a.layout}_V{V}_S{S}_B{B}_per_gpu",
                        "global_batch": world * B, "seq_len": 30, "parallelism": f"dp{world}",
-                       "joints": V, "imu_axes": S, "classes": C, "rgb_branch": "build-defined, timed on its own (rgb_branch key)",
+                       "joints": V, "imu_axes": S, "classes": C, "rgb_branch": "build-defined, timed on its own (rgb_branch key, --full)",
                        "hip_graph": bool(a.graph and not a.no_graph), "final_loss": round(loss, 5),
                        "ranks": world, "collective": "rccl all_reduce (2 buckets, high-priority streams)" if world > 1 else None},
-            "roofline": roofs.get("dgrad_l8", roofs.get("wgrad_l1", roofs["tcn_fwd"])),
+            "roofline": roofs.get("dgrad_l8", roofs.get("wgrad_l1", roofs.get("tcn_fwd"))),
             "roofline_wgrad_l1": roofs.get("wgrad_l1"),
             "roofline_wgrad_l5": roofs.get("wgrad_l5"),
             "roofline_wgrad_l6": roofs.get("wgrad"),
             "roofline_wgrad_kernel": roofs.get("wgrad_kernel"),
-            "roofline_tcn_fwd": roofs["tcn_fwd"],
+            "roofline_tcn_fwd": roofs.get("tcn_fwd"),
             "roofline_graph_mix": mix,
             "roofline_gcn": _gcn_roofline(roofs),
             "step_mfma": {"flop_per_clip": FLOP_PER_CLIP.get((V, S)), "achieved_tflops": None if FLOP_PER_CLIP.get(
@@ -1143,6 +1200,8 @@ def main():
             "cpu_baseline": cpu,
             "reference_cpu_published": REFERENCE_CPU,
         }
+        if not a.full:
+            rec = {k: v for k, v in rec.items() if k not in FULL_KEYS}
         print(json.dumps(rec), flush=True)
     if world > 1:
         dist.destroy_process_group()

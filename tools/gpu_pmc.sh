@@ -5,7 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS=${ARGS:-"--no-cpu-baseline --steps 3 --warmup 1"}
+ARGS=${ARGS:-"--full --no-cpu-baseline --steps 3 --warmup 1"}
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 120 rocprofv3 --pmc $C --kernel-trace -d gpurun_out/pmc_$C -o run -- python bench.py $ARGS \
       > gpurun_out/pmc_$C.log 2>&1 || { echo "pmc $C failed"; tail -20 gpurun_out/pmc_$C.log; exit 1; }

@@ -17,8 +17,9 @@
 #               ${ROOF_KEYS:-wgrad_l1 dgrad_l8 wgrad_l5 wgrad wgrad_kernel tcn_fwd gcn_l5 gcn_l6}          -> gpurun_out/roof_kernels_KEY.txt
 #   roof_pmc    FETCH_SIZE / WRITE_SIZE passes of the same, per key     -> gpurun_out/roofline_pmc.json
 #   rgb_pmc     FETCH_SIZE / WRITE_SIZE passes of the RGB branch kernels -> gpurun_out/rgb_pmc.json
-#   bench       bench.py (default run, 20 steps)                        -> gpurun_out/bench.json
-#   bench_fp32  bench.py --precision fp32 --no-targcn                   -> gpurun_out/bench_fp32.json
+#   bench       bench.py --full (every leg, 20 steps)                   -> $OUT/bench.json
+#   bench_fp32  bench.py --full --precision fp32 --no-targcn            -> $OUT/bench_fp32.json
+#               (OUT: where the two bench steps write, default bench_out/)
 #   ab          tools/ab.sh env $AB_CFGS (eager bench A/B, optional serial profiles) -> gpurun_out/ab.log
 #   bench_tg    bench.py --model targcn per TG_CFGS config                -> gpurun_out/bench_tg_*.json
 #   smoke       __graft_entry__.smoke()
@@ -27,6 +28,8 @@
 set -o pipefail
 mkdir -p gpurun_out
 export TMPDIR=/tmp
+OUT=${OUT:-bench_out}
+mkdir -p "$OUT"
 # raw rocprofv3 databases stay on the box (gpurun copies back at most 64 MiB of gpurun_out/); only the
 # summaries made from them go to gpurun_out/
 export PROF_DIR=${PROF_DIR:-/tmp/f3prof}
@@ -144,12 +147,12 @@ for step in "$@"; do
       python tools/rgb_pmc.py gpurun_out > gpurun_out/rgb_pmc.json 2>&1
       cat gpurun_out/rgb_pmc.json ;;
     bench)
-      run bench 600 python bench.py --steps 20 --warmup 5 > gpurun_out/bench.json 2> gpurun_out/bench.err
-      cut -c1-600 gpurun_out/bench.json ;;
+      run bench 600 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+      cut -c1-600 "$OUT/bench.json" ;;
     bench_fp32)
-      run bench_fp32 300 python bench.py --steps 20 --warmup 5 --precision fp32 --no-targcn --no-cpu-baseline \
-        > gpurun_out/bench_fp32.json 2> gpurun_out/bench_fp32.err
-      cut -c1-400 gpurun_out/bench_fp32.json ;;
+      run bench_fp32 300 python bench.py --full --steps 20 --warmup 5 --precision fp32 --no-targcn --no-cpu-baseline \
+        > "$OUT/bench_fp32.json" 2> "$OUT/bench_fp32.err"
+      cut -c1-400 "$OUT/bench_fp32.json" ;;
     ab)   # eager bench A/B over AB_CFGS (tools/ab.sh env; SERIAL_PROF / PAT / ROUNDS pass through)
       run ab 900 bash tools/ab.sh env ${AB_CFGS:--} > gpurun_out/ab.log 2>&1
       grep -E "ms/step|==" gpurun_out/ab.log | head -40 ;;
