@@ -51,6 +51,23 @@ struct MixArgs {
 };
 constexpr int kMixParts = 1024;
 
+// bf16x3: the gcn input gradient fused into the graph-mix backward (gcn_bwd.hip); dZ stays on chip
+struct GcnDgradMixArgs {
+  int frames, K, V, Cin, C;
+  const unsigned short* dg;  // [frames * V] rows [hi | lo] of 2 C bf16
+  const unsigned short* w;   // packed transposed split gcn weight [K * Cin][2 C] (prep code 4)
+  const float* A;            // A_eff [K][V][V]
+  const float* x;            // fp32 [frames][V][Cin]
+  float* dx;                 // fp32 [frames][V][Cin]
+  float* dA;                 // accumulated [K][V][V] (unless no_colsum)
+  int accumulate;            // dx += (identity residual)
+  float* part;               // dA partial rows [f3_gcn_dgrad_mix_parts][K * V * V]
+  int no_colsum;             // leave the partial rows in `part` (the caller sums them)
+  int max_workgroups;        // 0: one round of resident workgroups; > 0: this many (rounded down to whole
+                             // frame slots). The step passes mix_bwd_x3's count, so dA's partial rows hold
+                             // the same frames and sum to the same bits; tests pass a few
+};
+
 // the first block's graph convolution (Cin <= 4, C = 64) in the bf16 mode (layer0.hip)
 struct Gcn0Args {
   int frames, K, V, Ci;
@@ -230,6 +247,9 @@ int f3_databn_bwd(const f3::DataBnArgs* a, hipStream_t s);
 int f3_mix_fwd(const f3::MixArgs* a, hipStream_t s);
 int f3_mix_bwd(const f3::MixArgs* a, hipStream_t s);
 int f3_mix_bwd_parts(const f3::MixArgs* a);  // dA partial rows the LDS mix backward leaves (0: none)
+bool f3_gcn_dgrad_mix_ok(int K, int V, int Cin, int C);  // shapes gcn_bwd.hip covers
+int f3_gcn_dgrad_mix(const f3::GcnDgradMixArgs* a, hipStream_t s);
+int f3_gcn_dgrad_mix_parts(const f3::GcnDgradMixArgs* a);  // dA partial rows the launch leaves
 bool f3_mix_lds_ok(int K, int V, int Cin);  // the LDS/MFMA mix path (takes bf16 dZ)
 bool f3_mix_x3_ok(int K, int V, int Cin);   // the split-bf16 mix kernels (bf16x3 mode; MixArgs::z3)
 int f3_split_x3(const float* x, unsigned short* out, long long rows, int C, hipStream_t s);  // [hi | lo] rows

@@ -581,6 +581,13 @@ inline void x3_gemm(ConvGemmArgs& a, int C) {
   a.g.lda = 2 * C;
 }
 
+// F3_GCN_DGRAD_FUSED=0: the gcn input-gradient GEMM and the mix backward as two kernels through an
+// fp32 dZ in HBM (the A/B baseline of gcn_bwd.hip's fused kernel); read once per process
+inline bool gcn_dgrad_fused() {
+  static const bool on = !getenv("F3_GCN_DGRAD_FUSED") || atoi(getenv("F3_GCN_DGRAD_FUSED")) != 0;
+  return on;
+}
+
 // prep code of the packed GEMM weights: 0 fp32, 1 bf16, 2 split hi / lo planes
 inline int wcode(const f3_net& n) { return n.cfg.precision == F3_PRECISION_BF16 ? 1 : is_x3(n) ? 2 : 0; }
 // bf16 view of an activation slot (bf16 mode stores GEMM operand tensors as bf16)
@@ -899,14 +906,28 @@ int stream_backward(const f3_net& net, int si, int N, const Ptrs& q, Ws& w, cons
       if (!f3_igemm_ok(gd)) return F3_EINVAL;
       gd.outb = bfa(W.dZ, 1);
     }
-    if ((part & 1) && !g0) F3_TRY(f3_conv_gemm(&gd, 0, 0, s));
+    // bf16x3: dZ, dx and dA in one pass over dg and x (gcn_bwd.hip), dZ never in HBM. Ci = 64 only:
+    // there the fused kernel makes the pair's sums in the pair's order (one channel chunk, the mix
+    // backward's frame-to-row map below), so the step's results are the same bits. With Ci / 64 chunks
+    // in separate workgroups dA would be summed in another order, and RMSprop turns last-bit gradient
+    // differences into different trajectories within a few steps.
+    const bool gfuse = gcat && !g0 && Ci == 64 && gcn_dgrad_fused() && f3_gcn_dgrad_mix_ok(K, V, Ci, C);
+    GcnDgradMixArgs gf;
+    std::memset(&gf, 0, sizeof(gf));
+    if (gfuse) {
+      gf.frames = N * Ti; gf.K = K; gf.V = V; gf.Cin = Ci; gf.C = C; gf.dg = bfa(dg, 1); gf.w = bf(X.gwT, 1);
+      gf.A = X.aeff; gf.x = X.x; gf.dx = dx; gf.dA = X.dAeff; gf.accumulate = L.res == RES_ID;
+      gf.part = X.mixpart; gf.no_colsum = split;
+    }
+    if ((part & 1) && !g0 && !gfuse) F3_TRY(f3_conv_gemm(&gd, 0, 0, s));
     MixArgs mx;
     std::memset(&mx, 0, sizeof(mx));
     mx.K = K; mx.V = V; mx.Cin = Ci; mx.frames = N * Ti; mx.A = X.aeff; mx.x = X.x; mx.z = W.dZ;
     mx.dx = dx; mx.dA = X.dAeff; mx.accumulate = L.res == RES_ID; mx.part = X.mixpart; mx.x16 = hb;
     mx.no_colsum = split; mx.x3 = x3;
     mx.dzb = dzb ? bfa(W.dZ, 1) : nullptr;
-    if (part & 1) F3_TRY(g0 ? f3_gcn0_bwd(&b0, s) : f3_mix_bwd(&mx, s));
+    if (gfuse) gf.max_workgroups = f3_mix_bwd_parts(&mx);  // row r: frames r, r + rows, ... as mix_bwd_x3
+    if (part & 1) F3_TRY(g0 ? f3_gcn0_bwd(&b0, s) : gfuse ? f3_gcn_dgrad_mix(&gf, s) : f3_mix_bwd(&mx, s));
     if (L.res == RES_CONV) {
       ConvGemmArgs rd;
       std::memset(&rd, 0, sizeof(rd));
@@ -980,7 +1001,7 @@ int stream_backward(const f3_net& net, int si, int N, const Ptrs& q, Ws& w, cons
     if (split) {  // reductions whose results only feed weight gradients
       const int T = L.T_in, fch = f3_bn_bwd_parts(N, T * V, V);
       if (part & 2) cj[ncj++] = {X.gpart, X.G, (long long)V * C, fch, V * C};
-      const int mparts = g0 ? 0 : f3_mix_bwd_parts(&mx);
+      const int mparts = g0 ? 0 : gfuse ? f3_gcn_dgrad_mix_parts(&gf) : f3_mix_bwd_parts(&mx);
       if (mparts && (part & 2)) cj[ncj++] = {X.mixpart, X.dAeff, (long long)K * V * V, mparts, K * V * V};
     }
     if (g0 && (part & 2)) {  // the first block's dA_eff and gcn weight gradient partial rows
@@ -1958,6 +1979,30 @@ int f3_graph_mix_backward_ex(const float* A_eff, const void* x, const void* dz, 
   if (!part && hipMalloc(&part, sizeof(float) * kMixParts * 1024) != hipSuccess) return F3_EHIP;
   m.part = part;
   return f3_mix_bwd(&m, s);
+}
+
+int f3_gcn_dgrad_mix_x3(const void* dg3, const float* w, void* wpack, const float* A_eff, const float* x, float* dx,
+                        float* dA, int frames, int K, int V, int Cin, int C, int accumulate, int max_workgroups,
+                        void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!dg3 || !wpack || !A_eff || !x || !dx || !dA || frames < 0 || max_workgroups < 0) return F3_EINVAL;
+  if (!f3_gcn_dgrad_mix_ok(K, V, Cin, C) || K * V * V > 1024) return F3_EINVAL;  // (the scratch rows below)
+  if (w) {  // the step's transposed packing of w [C][K Cin] (w == NULL: wpack already packed)
+    PrepTable t;
+    t.n = 0;
+    add_job(t, PREP_PACK_CONV_T, C * K * Cin * x3mul(x3code()), static_cast<float*>(wpack), w, nullptr, nullptr, C,
+            K * Cin, 1, x3code());
+    F3_TRY(f3_prep(t, s));
+  }
+  if (hipMemsetAsync(dA, 0, sizeof(float) * K * V * V, s) != hipSuccess) return F3_EHIP;
+  static float* part = nullptr;  // test entry only: scratch kept for the process lifetime
+  if (!part && hipMalloc(&part, sizeof(float) * kMixParts * 1024) != hipSuccess) return F3_EHIP;
+  GcnDgradMixArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.frames = frames; a.K = K; a.V = V; a.Cin = Cin; a.C = C; a.dg = static_cast<const unsigned short*>(dg3);
+  a.w = static_cast<const unsigned short*>(wpack); a.A = A_eff; a.x = x; a.dx = dx; a.dA = dA;
+  a.accumulate = accumulate != 0; a.part = part; a.max_workgroups = max_workgroups;
+  return f3_gcn_dgrad_mix(&a, s);
 }
 
 // debug accessor (tests/tools only): device pointer of a named per-layer workspace tensor

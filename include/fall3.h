@@ -245,6 +245,16 @@ int f3_graph_mix_forward_ex(const float* A_eff, const void* x, void* z, int fram
                             void* stream);
 int f3_graph_mix_backward_ex(const float* A_eff, const void* x, const void* dz, float* dx, float* dA, int frames, int K,
                              int V, int Cin, int flags, void* stream);
+/* bf16x3 step: the gcn 1x1 input gradient fused into the graph-mix backward (dZ stays on chip), as
+ * stream_backward launches it. dg3: rows [dg_hi | dg_lo] of 2 C bf16 per (frame, node), as f3_split_x3cat
+ * writes; w [C][K Cin] is packed into wpack (2 C K Cin bf16) when non-NULL. dx [frames][V][Cin] is
+ * overwritten, or added to when accumulate; dA [K][V][V] is overwritten. max_workgroups > 0 sets the
+ * grid (a small test makes one workgroup walk several frames; the step passes the mix backward's
+ * count); 0 = one round of resident workgroups. F3_EINVAL outside
+ * Cin, C in {64, 128, 256}, C >= Cin, K <= 3, V <= 32, K V <= 64. */
+int f3_gcn_dgrad_mix_x3(const void* dg3, const float* w, void* wpack, const float* A_eff, const float* x, float* dx,
+                        float* dA, int frames, int K, int V, int Cin, int C, int accumulate, int max_workgroups,
+                        void* stream);
 
 const char* f3_status_string(int status);
 
