@@ -17,7 +17,7 @@ from .config import CfgNode, get_cfg_defaults
 from .graph import Graph
 from .model import (BiLSTM, CNN_BiLSTM, Fall3Net, NetSpec, STGCAN, TwoStreamSpatialTemporalGraph, TwoStreamSTGCAN,
                     TwoStreamSTGCAN_BiLSTM, build_model)
-from .optim import RMSprop, build_optimizer
+from .optim import SGD, Adam, AdamW, RMSprop, build_optimizer
 from .train import TrainStep
 from .targcn import TARGCN, TargcnStep
 from .sktr import SkeletonTransformer, SktrStep
@@ -26,4 +26,4 @@ from . import data, evaluate
 
 __all__ = ["build_model", "build_optimizer", "get_cfg_defaults", "CfgNode", "Graph", "Fall3Net", "NetSpec",
            "STGCAN", "BiLSTM", "CNN_BiLSTM", "TwoStreamSTGCAN", "TwoStreamSTGCAN_BiLSTM", "TwoStreamSpatialTemporalGraph",
-           "RMSprop", "TrainStep", "TARGCN", "TargcnStep", "SkeletonTransformer", "SktrStep", "musa", "data", "evaluate"]
+           "RMSprop", "SGD", "Adam", "AdamW", "TrainStep", "TARGCN", "TargcnStep", "SkeletonTransformer", "SktrStep", "musa", "data", "evaluate"]

@@ -32,10 +32,22 @@ EXPORTS = (
     "f3_musa_buffer_count", "f3_musa_counter_count", "f3_musa_workspace_bytes", "f3_musa_forward", "f3_musa_backward",
     "f3_musa_guards",
     "f3_dwconv_t_forward", "f3_pointwise_conv", "f3_rgb_scratch_floats", "f3_rgb_forward", "f3_rgb_backward",
+    "f3_optim_scalars_bytes", "f3_optim_step", "f3_optim_step_ranges", "f3_net_backward_optim", "f3_net_entry_nograd",
 )
 
 F3_OK, F3_EINVAL, F3_EBATCH, F3_EHIP, F3_ESTATE, F3_EDEVICE = 0, 1001, 1002, 1003, 1004, 1005
 ENTRY_PARAM, ENTRY_BUFFER, ENTRY_COUNTER = 0, 1, 2
+OPT_RMSPROP, OPT_SGD, OPT_ADAM, OPT_ADAMW = 0, 1, 2, 3
+OPT_MAX_SKIP = 4
+
+
+class F3OptimConfig(ctypes.Structure):
+    """f3_optim_config (include/fall3.h)."""
+    _fields_ = ([("kind", ctypes.c_int), ("nesterov", ctypes.c_int)]
+                + [(n, ctypes.c_double) for n in ("lr", "alpha", "eps", "momentum", "beta1", "beta2", "weight_decay",
+                                                  "max_norm", "grad_scale")]
+                + [("nskip", ctypes.c_int), ("skip_lo", ctypes.c_int64 * OPT_MAX_SKIP),
+                   ("skip_len", ctypes.c_int64 * OPT_MAX_SKIP)])
 
 
 class F3TargcnConfig(ctypes.Structure):
@@ -88,6 +100,12 @@ def lib():
         "f3_net_precision": (I, [P]),
         "f3_net_status": (I, [P, I]),
         "f3_rmsprop_step": (I, [P, P, P, I64, F, F, F, F, P]),
+        "f3_optim_scalars_bytes": (I64, []),
+        "f3_optim_step": (I, [ctypes.POINTER(F3OptimConfig), P, P, P, P, I64, P, P]),
+        "f3_optim_step_ranges": (I, [ctypes.POINTER(F3OptimConfig), P, P, P, P, I, ctypes.POINTER(I64),
+                                     ctypes.POINTER(I64), P, P]),
+        "f3_net_backward_optim": (I, [P, I, P, P, P, P, P, P, P, ctypes.POINTER(F3OptimConfig), P]),
+        "f3_net_entry_nograd": (I, [P, I]),
         "f3_conv_forward": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
         "f3_status_string": (ctypes.c_char_p, [I]),
         "f3_net_debug_tensor": (P, [P, I, P, I, I, ctypes.c_char_p]),

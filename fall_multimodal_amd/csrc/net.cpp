@@ -34,6 +34,9 @@ struct Entry {
   std::vector<int64_t> shape;
   int64_t offset, numel;
   int phase;  // params: backward phase that finalises the gradient (1 = head side, 2 = input side)
+  // a parameter no backward writes (.grad stays None in the reference): torch.optim keeps no state for
+  // it and applies no decay, so f3_net_backward_optim / f3_optim_step leave it out (f3_net_entry_nograd)
+  bool nograd = false;
 };
 
 // Backward runs in two phases so DP can all-reduce the first phase's gradients while the
@@ -129,6 +132,9 @@ struct f3_net {
   // f3_net_backward_rmsprop's plan, fixed by the parameter layout: computed once (first call)
   int fused_opt = -1;                  // -1 unknown, 0 one update after the backward, 1 per layer
   std::vector<RmsRanges> rest_ranges;  // parameters outside the skeleton layers' ranges
+  // f3_net_backward_optim: the same without the no-gradient entries, and those entries as a skip list
+  std::vector<RmsRanges> rest_ranges_opt;
+  OptSkip nograd_skip{0, {}, {}};
   int add(const std::string& name, int kind, std::vector<int64_t> shape) {
     Entry e;
     e.name = name;
@@ -242,6 +248,7 @@ struct f3_net {
     cnn.bn2 = add_bn(p + "layer2.1", 32);
     cnn.fcw = add(p + "fc.weight", F3_ENTRY_PARAM, {32, 32 * ((T / 2) / 2)});  // unused in forward
     cnn.fcb = add(p + "fc.bias", F3_ENTRY_PARAM, {32});
+    entries[cnn.fcw].nograd = entries[cnn.fcb].nograd = true;
   }
 };
 
@@ -518,6 +525,7 @@ struct Ptrs {
   float* opt_p = nullptr;
   float* opt_sq = nullptr;
   float lr = 0.f, alpha = 0.f, eps = 0.f;
+  const OptLaunch* opt_gen = nullptr;  // f3_net_backward_optim: the update of opt_gen instead of RMSprop
   const float* p(int i) const { return P + net.entries[i].offset; }
   float* g(int i) const { return G + net.entries[i].offset; }
   float* b(int i) const { return B + net.entries[i].offset; }
@@ -1039,7 +1047,9 @@ int stream_backward(const f3_net& net, int si, int N, const Ptrs& q, Ws& w, cons
     if (part & 2) F3_TRY(f3_gcn_bias_bwd(&gb, ss));
     // fused optimizer: every gradient of this layer is final here on ss (its main-chain parts were
     // waited for through ev_main), and nothing later in the backward reads these parameters
-    if (q.opt_p && (part & 2))
+    if (q.opt_gen && (part & 2))
+      F3_TRY(f3_optim_ranges(*q.opt_gen, layer_ranges(net, L), ss));
+    else if (q.opt_p && (part & 2))
       F3_TRY(f3_rmsprop_ranges(q.opt_p, q.opt_sq, q.G, layer_ranges(net, L), q.lr, q.alpha, q.eps, 1.f, ss));
     dout = dx;
     pp ^= 1;
@@ -1420,6 +1430,7 @@ namespace {
 struct FusedOpt {
   float *p, *sq;
   float lr, alpha, eps;
+  const OptLaunch* gen = nullptr;  // f3_net_backward_optim
 };
 
 int net_backward(f3_net* net, int N, const float* params, const float* dout, float* grads, void* workspace, int phase,
@@ -1449,8 +1460,19 @@ bool layer_ranges_ok(const f3_net& n) {
 void fused_opt_plan(f3_net& n) {
   n.fused_opt = layer_ranges_ok(n);
   n.rest_ranges.clear();
+  n.rest_ranges_opt.clear();
+  // the no-gradient entries (whole padded entries, adjacent ones merged) for the flat update
+  n.nograd_skip.n = 0;
+  for (const Entry& e : n.entries) {
+    if (e.kind != F3_ENTRY_PARAM || !e.nograd) continue;
+    OptSkip& k = n.nograd_skip;
+    const long long lo = e.offset, len = (e.numel + 3) / 4 * 4;
+    if (k.n && k.lo[k.n - 1] + k.len[k.n - 1] == lo) k.len[k.n - 1] += len;
+    else if (k.n < kOptSkip) { k.lo[k.n] = lo; k.len[k.n] = len; ++k.n; }
+    else { n.nograd_skip.n = -1; break; }  // more ranges than the kernel takes: f3_net_backward_optim refuses
+  }
   if (!n.fused_opt) return;
-  std::vector<std::pair<long long, long long>> done, rest;
+  std::vector<std::pair<long long, long long>> done, rest, rest_opt;
   for (int si = 0; si < n.nstreams; ++si)
     for (int l = 0; l < 7; ++l) {
       const RmsRanges r = layer_ranges(n, n.st[si].L[l]);
@@ -1464,17 +1486,24 @@ void fused_opt_plan(f3_net& n) {
     const long long lo = e.offset, hi = e.offset + (e.numel + 3) / 4 * 4;
     if (!rest.empty() && rest.back().second == lo) rest.back().second = hi;
     else rest.push_back({lo, hi});
+    if (e.nograd) continue;
+    if (!rest_opt.empty() && rest_opt.back().second == lo) rest_opt.back().second = hi;
+    else rest_opt.push_back({lo, hi});
   }
-  RmsRanges r;
-  r.n = 0;
-  for (size_t i = 0; i < rest.size(); ++i) {
-    r.lo[r.n] = rest[i].first;
-    r.len[r.n] = rest[i].second - rest[i].first;
-    if (++r.n == kRmsRanges || i + 1 == rest.size()) {
-      n.rest_ranges.push_back(r);
-      r.n = 0;
+  auto pack = [](const std::vector<std::pair<long long, long long>>& v, std::vector<RmsRanges>& out) {
+    RmsRanges r;
+    r.n = 0;
+    for (size_t i = 0; i < v.size(); ++i) {
+      r.lo[r.n] = v[i].first;
+      r.len[r.n] = v[i].second - v[i].first;
+      if (++r.n == kRmsRanges || i + 1 == v.size()) {
+        out.push_back(r);
+        r.n = 0;
+      }
     }
-  }
+  };
+  pack(rest, n.rest_ranges);
+  pack(rest_opt, n.rest_ranges_opt);
 }
 }  // namespace
 
@@ -1491,12 +1520,41 @@ int f3_net_backward_rmsprop(f3_net* net, int N, float* params, const float* dout
     F3_TRY(net_backward(net, N, params, dout, grads, workspace, 0, stream, nullptr));
     return f3_rmsprop(params, square_avg, grads, net->nparam, lr, alpha, eps, 1.f, s);
   }
-  const FusedOpt o{params, square_avg, lr, alpha, eps};
+  const FusedOpt o{params, square_avg, lr, alpha, eps, nullptr};
   F3_TRY(net_backward(net, N, params, dout, grads, workspace, 0, stream, &o));
   // every parameter outside the layers' ranges (data_bn, sensor branch, head), after the join
   for (const RmsRanges& r : net->rest_ranges)
     F3_TRY(f3_rmsprop_ranges(params, square_avg, grads, r, lr, alpha, eps, 1.f, s));
   return F3_OK;
+}
+
+int f3_net_backward_optim(f3_net* net, int N, float* params, const float* dout, float* grads, float* state0,
+                          float* state1, void* scalars, void* workspace, const f3_optim_config* cfg, void* stream) {
+  if (!net || !grads) return F3_EINVAL;
+  OptLaunch o;
+  F3_TRY(f3_optim_resolve(cfg, params, state0, state1, grads, scalars, &o));
+  hipStream_t s = (hipStream_t)stream;
+  if (net->fused_opt < 0) fused_opt_plan(*net);
+  if (net->nograd_skip.n < 0) return F3_EINVAL;
+  // clipping: the norm needs every gradient, so one flat update after the join (as the layouts without
+  // contiguous per-layer ranges)
+  if (!net->fused_opt || o.max_norm > 0.0) {
+    F3_TRY(net_backward(net, N, params, dout, grads, workspace, 0, stream, nullptr));
+    F3_TRY(f3_optim_begin(o, net->nparam, s));
+    return f3_optim_flat(o, net->nparam, net->nograd_skip, s);
+  }
+  // the begin kernel on the caller's stream before the backward forks its private queues: every
+  // per-layer update is ordered after it
+  F3_TRY(f3_optim_begin(o, net->nparam, s));
+  FusedOpt fo{params, state0, (float)o.lr, (float)o.alpha, (float)o.eps, &o};
+  F3_TRY(net_backward(net, N, params, dout, grads, workspace, 0, stream, &fo));
+  for (const RmsRanges& r : net->rest_ranges_opt) F3_TRY(f3_optim_ranges(o, r, s));
+  return F3_OK;
+}
+
+int f3_net_entry_nograd(const f3_net* net, int i) {
+  if (!net || i < 0 || i >= (int)net->entries.size()) return -1;
+  return net->entries[i].nograd ? 1 : 0;
 }
 
 int f3_net_fused_rmsprop(f3_net* net) {
@@ -1531,6 +1589,7 @@ int net_backward(f3_net* net, int N, const float* params, const float* dout, flo
   Ptrs q{*net, params, nullptr, nullptr, grads};
   if (opt) {
     q.opt_p = opt->p; q.opt_sq = opt->sq; q.lr = opt->lr; q.alpha = opt->alpha; q.eps = opt->eps;
+    q.opt_gen = opt->gen;
   }
   // skeleton streams layer by layer, interleaved (see stream_forward)
   // after_first: called once the first layer's main chains are submitted (the sensor backward, so its

@@ -1,0 +1,327 @@
+// The optimizers of build_optimizer besides plain RMSprop (Multimodal_Fall3/model/optimizer.py:20-29:
+// torch.optim.SGD / Adam / AdamW; RMSprop with weight decay) and the root driver's global gradient-norm
+// clipping (Multimodal_Fall3/main.py:108-113 clip_grad_norm_), as flat updates over the one parameter
+// buffer. Formulas: include/fall3.h (f3_optim_config).
+//
+// Every launch of one step reads the step scalars (OptScalars) that the step's begin kernel wrote, so
+// the Adam step count lives on the device and a replayed graph advances it. The state recurrences
+// (momentum buffer, exp_avg, exp_avg_sq, square_avg) and the effective gradient are evaluated in fp64
+// and rounded to fp32 once: m + (1-b1)(g - m) cancels, and an fp32 evaluation loses relative accuracy
+// of the result exactly there. The kernels are memory bound (3-4 loads, 2-3 stores per element), so
+// the fp64 VALU work is free. The one sqrt and the one division per element are fp32.
+#include <cmath>
+
+#include "common.h"
+#include "sensor.h"
+#include "fall3.h"
+
+namespace f3 {
+
+// kernel variants: the F3_OPT_* kinds, and SGD without a momentum buffer
+enum { OK_RMS = 0, OK_SGD = 1, OK_ADAM = 2, OK_ADAMW = 3, OK_SGD0 = 4 };
+
+struct OptArgs {
+  double lr, a, oma, mu, b1, omb1, b2, omb2, wd, gscale;
+  float lr_f, eps_f;
+  int nesterov;
+};
+
+// One element. contract(off): the flat and the ranges kernel, and the vector body and the scalar tail,
+// must round identically (the per-layer updates are compared bit for bit with the flat one).
+template <int KIND>
+F3_DEV void opt_update(float& p, float& s0, float& s1, float grad, const OptArgs& a, double sg, float bc1,
+                       float bc2s) {
+#pragma clang fp contract(off)
+  double g = sg * (double)grad;
+  double pd = (double)p;
+  if (KIND == OK_ADAMW) pd = pd * (1.0 - a.lr * a.wd);
+  else g = g + a.wd * pd;
+  if (KIND == OK_RMS) {
+    const float sq = (float)(a.a * (double)s0 + a.oma * g * g);
+    s0 = sq;
+    p = p - a.lr_f * (float)g / (sqrtf(sq) + a.eps_f);
+  } else if (KIND == OK_SGD) {
+    const float buf = (float)(a.mu * (double)s0 + g);
+    s0 = buf;
+    const double d = a.nesterov ? g + a.mu * (double)buf : (double)buf;
+    p = (float)(pd - a.lr * d);
+  } else if (KIND == OK_SGD0) {
+    p = (float)(pd - a.lr * g);
+  } else {
+    const float m = (float)((double)s0 + a.omb1 * (g - (double)s0));
+    const float v = (float)(a.b2 * (double)s1 + a.omb2 * g * g);
+    s0 = m;
+    s1 = v;
+    const float q = m / (sqrtf(v) * bc2s + a.eps_f);
+    p = (float)(pd - (a.lr * (double)bc1) * (double)q);
+  }
+}
+
+template <int KIND>
+F3_DEV void opt_update4(float* __restrict__ p, float* __restrict__ s0, float* __restrict__ s1,
+                        const float* __restrict__ g, long long i4, const OptArgs& a, double sg, float bc1,
+                        float bc2s) {
+  constexpr bool has0 = KIND != OK_SGD0, has1 = KIND == OK_ADAM || KIND == OK_ADAMW;
+  const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i4];
+  f32x4 pv = reinterpret_cast<f32x4*>(p)[i4];
+  f32x4 av = {0.f, 0.f, 0.f, 0.f}, bv = {0.f, 0.f, 0.f, 0.f};
+  if (has0) av = reinterpret_cast<f32x4*>(s0)[i4];
+  if (has1) bv = reinterpret_cast<f32x4*>(s1)[i4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float pe = pv[e], ae = av[e], be = bv[e];
+    opt_update<KIND>(pe, ae, be, gv[e], a, sg, bc1, bc2s);
+    pv[e] = pe; av[e] = ae; bv[e] = be;
+  }
+  reinterpret_cast<f32x4*>(p)[i4] = pv;
+  if (has0) reinterpret_cast<f32x4*>(s0)[i4] = av;
+  if (has1) reinterpret_cast<f32x4*>(s1)[i4] = bv;
+}
+
+F3_DEV bool opt_skipped(const OptSkip& k, long long i) {
+  bool in = false;
+  for (int j = 0; j < k.n; ++j) in = in || (i >= k.lo[j] && i < k.lo[j] + k.len[j]);
+  return in;
+}
+
+// flat shape: float4 body + scalar tail over n floats, grid-stride (as rmsprop_kernel)
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, float* __restrict__ s0,
+                                                    float* __restrict__ s1, const float* __restrict__ g,
+                                                    long long n, OptArgs a, OptSkip skip,
+                                                    const OptScalars* __restrict__ sc) {
+  const double sg = a.gscale * (double)sc->clip_coef;
+  const float bc1 = sc->bc1, bc2s = sc->bc2s;
+  const long long n4 = n / 4;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long t0 = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  for (long long i = t0; i < n4; i += stride) {
+    if (skip.n && opt_skipped(skip, i * 4)) continue;  // skip ranges are whole float4s
+    opt_update4<KIND>(p, s0, s1, g, i, a, sg, bc1, bc2s);
+  }
+  for (long long i = n4 * 4 + t0; i < n; i += stride) {
+    if (skip.n && opt_skipped(skip, i)) continue;
+    float pe = p[i], ae = KIND != OK_SGD0 ? s0[i] : 0.f, be = (KIND == OK_ADAM || KIND == OK_ADAMW) ? s1[i] : 0.f;
+    opt_update<KIND>(pe, ae, be, g[i], a, sg, bc1, bc2s);
+    p[i] = pe;
+    if (KIND != OK_SGD0) s0[i] = ae;
+    if (KIND == OK_ADAM || KIND == OK_ADAMW) s1[i] = be;
+  }
+}
+
+// ranges shape (as rmsprop_ranges_kernel): n4 float4s spread over r.n 16-byte-aligned ranges
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_ranges_kernel(float* __restrict__ p, float* __restrict__ s0,
+                                                           float* __restrict__ s1, const float* __restrict__ g,
+                                                           RmsRanges r, long long n4, OptArgs a,
+                                                           const OptScalars* __restrict__ sc) {
+  const double sg = a.gscale * (double)sc->clip_coef;
+  const float bc1 = sc->bc1, bc2s = sc->bc2s;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    long long k = i;
+    int j = 0;
+    for (; j < r.n - 1 && k >= r.len[j] / 4; ++j) k -= r.len[j] / 4;
+    opt_update4<KIND>(p, s0, s1, g, r.lo[j] / 4 + k, a, sg, bc1, bc2s);
+  }
+}
+
+// sum g^2 in fp64 (an fp32 square is exact in fp64): workgroup b owns the fixed slice of float4s
+// [b * chunk4, (b+1) * chunk4), its threads stride through it, an LDS tree adds the 256 thread sums in a
+// fixed order, and the workgroup stores one partial. Block 0 also takes the n % 4 tail. No atomics.
+__global__ __launch_bounds__(256) void gradnorm_partials_kernel(const float* __restrict__ g, long long n,
+                                                                double* __restrict__ partials) {
+  __shared__ double sh[256];
+  const long long n4 = n / 4;
+  const long long chunk4 = (n4 + gridDim.x - 1) / gridDim.x;
+  const long long lo = blockIdx.x * chunk4;
+  const long long hi = lo + chunk4 < n4 ? lo + chunk4 : n4;
+  double acc = 0.0;
+  for (long long i = lo + threadIdx.x; i < hi; i += blockDim.x) {
+    const f32x4 v = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) acc += (double)v[e] * (double)v[e];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    for (long long i = n4 * 4; i < n; ++i) acc += (double)g[i] * (double)g[i];
+  sh[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) partials[blockIdx.x] = sh[0];
+}
+
+// once per optimizer step, one workgroup: t += 1, the bias corrections in fp64 from the integer t, the
+// norm from the partials in index order, the clip coefficient (clip_grad_norm_: max_norm / (norm + 1e-6),
+// clamped to 1; a non-finite norm propagates as in torch)
+__global__ void optim_begin_kernel(OptScalars* __restrict__ sc, int adam, double b1, double b2, double max_norm,
+                                   double gscale) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const long long t = sc->t + 1;
+  sc->t = t;
+  float bc1 = 1.f, bc2s = 1.f;
+  if (adam) {
+    bc1 = (float)(1.0 / (1.0 - pow(b1, (double)t)));
+    bc2s = (float)(1.0 / sqrt(1.0 - pow(b2, (double)t)));
+  }
+  sc->bc1 = bc1;
+  sc->bc2s = bc2s;
+  float coef = 1.f, norm = 0.f;
+  if (max_norm > 0.0) {
+    double sum = 0.0;
+    for (int i = 0; i < kNormBlocks; ++i) sum += sc->partials[i];
+    const double nd = gscale * sqrt(sum);
+    const double c = max_norm / (nd + 1e-6);
+    norm = (float)nd;
+    coef = (float)(c > 1.0 ? 1.0 : c);
+  }
+  sc->clip_coef = coef;
+  sc->grad_norm = norm;
+}
+
+}  // namespace f3
+
+using namespace f3;
+
+namespace {
+OptArgs opt_args(const OptLaunch& o) {
+  OptArgs a;
+  a.lr = o.lr; a.a = o.alpha; a.oma = 1.0 - o.alpha; a.mu = o.mu;
+  a.b1 = o.b1; a.omb1 = 1.0 - o.b1; a.b2 = o.b2; a.omb2 = 1.0 - o.b2; a.wd = o.wd; a.gscale = o.gscale;
+  a.lr_f = (float)o.lr; a.eps_f = (float)o.eps; a.nesterov = o.nesterov;
+  return a;
+}
+int opt_variant(const OptLaunch& o) { return o.kind == F3_OPT_SGD && o.mu == 0.0 ? (int)OK_SGD0 : o.kind; }
+int opt_grid(long long n4) {
+  const long long blocks = (n4 + 255) / 256;
+  return (int)(blocks < 4096 ? (blocks > 0 ? blocks : 1) : 4096);
+}
+bool finite_nonneg(double v) { return std::isfinite(v) && v >= 0.0; }
+}  // namespace
+
+int f3_optim_resolve(const f3_optim_config* c, float* p, float* s0, float* s1, const float* g, void* scalars,
+                     OptLaunch* o) {
+  if (!c || !p || !g || !scalars || (uintptr_t)scalars % 8) return F3_EINVAL;
+  if (c->kind < F3_OPT_RMSPROP || c->kind > F3_OPT_ADAMW) return F3_EINVAL;
+  if (!finite_nonneg(c->lr) || !finite_nonneg(c->weight_decay) || !finite_nonneg(c->max_norm) ||
+      !std::isfinite(c->grad_scale) || c->grad_scale <= 0.0)
+    return F3_EINVAL;
+  const bool adam = c->kind == F3_OPT_ADAM || c->kind == F3_OPT_ADAMW;
+  if (c->kind == F3_OPT_RMSPROP) {
+    if (c->momentum != 0.0) return F3_EINVAL;  // RMSprop momentum: not built
+    if (!finite_nonneg(c->alpha) || c->alpha >= 1.0 || !finite_nonneg(c->eps) || !s0) return F3_EINVAL;
+  } else if (c->kind == F3_OPT_SGD) {
+    if (!finite_nonneg(c->momentum)) return F3_EINVAL;
+    if (c->nesterov && c->momentum == 0.0) return F3_EINVAL;  // torch: nesterov needs a momentum
+    if (c->momentum != 0.0 && !s0) return F3_EINVAL;
+  } else {
+    if (!finite_nonneg(c->beta1) || c->beta1 >= 1.0 || !finite_nonneg(c->beta2) || c->beta2 >= 1.0 ||
+        !finite_nonneg(c->eps) || !s0 || !s1)
+      return F3_EINVAL;
+  }
+  o->kind = c->kind; o->nesterov = c->nesterov != 0;
+  o->lr = c->lr; o->alpha = c->alpha; o->eps = c->eps; o->mu = c->momentum;
+  o->b1 = adam ? c->beta1 : 0.0; o->b2 = adam ? c->beta2 : 0.0;
+  o->wd = c->weight_decay; o->max_norm = c->max_norm; o->gscale = c->grad_scale;
+  o->p = p; o->s0 = s0; o->s1 = s1; o->g = g; o->sc = static_cast<OptScalars*>(scalars);
+  return F3_OK;
+}
+
+int f3_optim_begin(const OptLaunch& o, long long n, hipStream_t s) {
+  if (n < 0 || (uintptr_t)o.g % 16) return F3_EINVAL;
+  if (o.max_norm > 0.0) {
+    hipLaunchKernelGGL(gradnorm_partials_kernel, dim3(kNormBlocks), dim3(256), 0, s, o.g, n, o.sc->partials);
+    F3_LAUNCH_CHECK();
+  }
+  const int adam = o.kind == F3_OPT_ADAM || o.kind == F3_OPT_ADAMW;
+  hipLaunchKernelGGL(optim_begin_kernel, dim3(1), dim3(64), 0, s, o.sc, adam, o.b1, o.b2, o.max_norm, o.gscale);
+  F3_LAUNCH_CHECK();
+  return F3_OK;
+}
+
+#define F3_OPT_DISPATCH(KERNEL, ...)                                                        \
+  switch (opt_variant(o)) {                                                                 \
+    case OK_RMS: hipLaunchKernelGGL(KERNEL<OK_RMS>, __VA_ARGS__); break;                    \
+    case OK_SGD: hipLaunchKernelGGL(KERNEL<OK_SGD>, __VA_ARGS__); break;                    \
+    case OK_SGD0: hipLaunchKernelGGL(KERNEL<OK_SGD0>, __VA_ARGS__); break;                  \
+    case OK_ADAM: hipLaunchKernelGGL(KERNEL<OK_ADAM>, __VA_ARGS__); break;                  \
+    default: hipLaunchKernelGGL(KERNEL<OK_ADAMW>, __VA_ARGS__); break;                      \
+  }
+
+int f3_optim_flat(const OptLaunch& o, long long n, const OptSkip& skip, hipStream_t s) {
+  if (n < 0 || skip.n < 0 || skip.n > kOptSkip) return F3_EINVAL;
+  for (int j = 0; j < skip.n; ++j)
+    if (skip.lo[j] % 4 || skip.len[j] % 4 || skip.lo[j] < 0 || skip.len[j] < 0) return F3_EINVAL;
+  if (((uintptr_t)o.p | (uintptr_t)o.s0 | (uintptr_t)o.s1 | (uintptr_t)o.g) % 16) return F3_EINVAL;
+  if (n == 0) return F3_OK;
+  if (o.legacy_rms())  // skipped entries carry a zero gradient: RMSprop without decay leaves them as they are
+    return f3_rmsprop(o.p, o.s0, o.g, n, (float)o.lr, (float)o.alpha, (float)o.eps, (float)o.gscale, s);
+  const OptArgs a = opt_args(o);
+  const OptScalars* sc = o.sc;
+  F3_OPT_DISPATCH(optim_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, o.p, o.s0, o.s1, o.g, n, a, skip, sc);
+  F3_LAUNCH_CHECK();
+  return F3_OK;
+}
+
+int f3_optim_ranges(const OptLaunch& o, const RmsRanges& r, hipStream_t s) {
+  if (o.max_norm > 0.0) return F3_EINVAL;  // the norm needs every gradient: flat update after the backward
+  if (o.legacy_rms())
+    return f3_rmsprop_ranges(o.p, o.s0, o.g, r, (float)o.lr, (float)o.alpha, (float)o.eps, (float)o.gscale, s);
+  if (r.n < 0 || r.n > kRmsRanges) return F3_EINVAL;
+  if (((uintptr_t)o.p | (uintptr_t)o.s0 | (uintptr_t)o.s1 | (uintptr_t)o.g) % 16) return F3_EINVAL;
+  long long n4 = 0;
+  for (int j = 0; j < r.n; ++j) {
+    if (r.lo[j] % 4 || r.len[j] % 4 || r.len[j] < 0 || r.lo[j] < 0) return F3_EINVAL;
+    n4 += r.len[j] / 4;
+  }
+  if (n4 == 0) return F3_OK;
+  const OptArgs a = opt_args(o);
+  const OptScalars* sc = o.sc;
+  F3_OPT_DISPATCH(optim_ranges_kernel, dim3(opt_grid(n4)), dim3(256), 0, s, o.p, o.s0, o.s1, o.g, r, n4, a, sc);
+  F3_LAUNCH_CHECK();
+  return F3_OK;
+}
+
+extern "C" {
+
+int64_t f3_optim_scalars_bytes(void) { return (int64_t)sizeof(OptScalars); }
+
+int f3_optim_step(const f3_optim_config* cfg, float* params, float* state0, float* state1, const float* grads,
+                  int64_t n, void* scalars, void* stream) {
+  OptLaunch o;
+  F3_TRY(f3_optim_resolve(cfg, params, state0, state1, grads, scalars, &o));
+  if (n < 0 || cfg->nskip < 0 || cfg->nskip > F3_OPT_MAX_SKIP) return F3_EINVAL;
+  OptSkip skip;
+  skip.n = cfg->nskip;
+  for (int j = 0; j < skip.n; ++j) {
+    skip.lo[j] = cfg->skip_lo[j];
+    skip.len[j] = cfg->skip_len[j];
+    if (skip.lo[j] < 0 || skip.len[j] < 0 || skip.lo[j] % 4 || skip.len[j] % 4 ||
+        skip.lo[j] + skip.len[j] > ((n + 3) / 4) * 4)
+      return F3_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  F3_TRY(f3_optim_begin(o, n, s));
+  return f3_optim_flat(o, n, skip, s);
+}
+
+int f3_optim_step_ranges(const f3_optim_config* cfg, float* params, float* state0, float* state1,
+                         const float* grads, int nranges, const int64_t* lo, const int64_t* len, void* scalars,
+                         void* stream) {
+  OptLaunch o;
+  F3_TRY(f3_optim_resolve(cfg, params, state0, state1, grads, scalars, &o));
+  if (nranges < 0 || nranges > kRmsRanges || (nranges && (!lo || !len)) || o.max_norm > 0.0) return F3_EINVAL;
+  RmsRanges r;
+  r.n = nranges;
+  for (int j = 0; j < nranges; ++j) {
+    r.lo[j] = lo[j];
+    r.len[j] = len[j];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  F3_TRY(f3_optim_begin(o, 0, s));
+  return f3_optim_ranges(o, r, s);
+}
+
+}  // extern "C"

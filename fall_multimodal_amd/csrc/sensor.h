@@ -141,3 +141,32 @@ int f3_rmsprop_ranges(float* p, float* sq, const float* g, const RmsRanges& r, f
                       float scale, hipStream_t s);
 int f3_rmsprop(float* p, float* sq, const float* g, long long n, float lr, float alpha, float eps, float scale,
                hipStream_t s);
+
+// SGD / Adam / AdamW / RMSprop-with-decay updates (optim.hip; arithmetic in include/fall3.h).
+constexpr int kNormBlocks = 256;  // the grad-norm reduction's fixed grid: one fp64 partial per workgroup
+struct OptScalars {               // the device block behind f3_optim_scalars_bytes()
+  long long t;
+  float bc1, bc2s, clip_coef, grad_norm;
+  double partials[kNormBlocks];
+};
+constexpr int kOptSkip = 4;
+struct OptSkip {
+  int n;
+  long long lo[kOptSkip], len[kOptSkip];
+};
+struct f3_optim_config;
+// one step's update launches: the hyper-parameters resolved on the host (fp64) and the buffers
+struct OptLaunch {
+  int kind, nesterov;
+  double lr, alpha, eps, mu, b1, b2, wd, max_norm, gscale;
+  float *p, *s0, *s1;
+  const float* g;
+  OptScalars* sc;
+  bool legacy_rms() const { return kind == 0 && wd == 0.0 && max_norm == 0.0; }  // rmsprop_kernel's bits
+};
+int f3_optim_resolve(const f3_optim_config* cfg, float* p, float* s0, float* s1, const float* g, void* scalars,
+                     OptLaunch* o);
+// [norm partials over g[0..n) when max_norm > 0,] then the begin kernel (t += 1, step scalars)
+int f3_optim_begin(const OptLaunch& o, long long n, hipStream_t s);
+int f3_optim_flat(const OptLaunch& o, long long n, const OptSkip& skip, hipStream_t s);
+int f3_optim_ranges(const OptLaunch& o, const RmsRanges& r, hipStream_t s);

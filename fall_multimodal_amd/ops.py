@@ -19,6 +19,10 @@ under torch.compile / FakeTensor tracing and composes with the rest of an autogr
   fall3::musa_backward(net, params, dout, workspace) -> grads
   fall3::rmsprop_(param!, square_avg!, grad, lr, alpha, eps, scale)
         optimizer.step(), model/optimizer.py:21 (torch.optim.RMSprop semantics)
+  fall3::optim_(param!, state0!, state1!, scalars!, grad, kind, nesterov, lr, alpha, eps, momentum, beta1, beta2,
+                weight_decay, max_norm, grad_scale, skip)
+        [clip_grad_norm_;] optimizer.step() for torch.optim.SGD / Adam / AdamW / RMSprop with weight decay,
+        model/optimizer.py:20-29, root main.py:108-113 (f3_optim_step)
 
 `net` is the integer id of a live native model (its f3_net / f3_targcn handle); `params` is the
 module's parameter list (views of one flat buffer, which the native call reads through). The ops
@@ -35,6 +39,7 @@ from typing import List, Optional, Tuple
 import torch
 from torch import Tensor
 
+from . import _lib
 from ._lib import check, lib, ptr, stream_handle
 
 _NETS: "weakref.WeakValueDictionary[int, object]" = weakref.WeakValueDictionary()
@@ -314,4 +319,55 @@ def rmsprop_(param: Tensor, square_avg: Tensor, grad: Tensor, lr: float, alpha: 
 
 @rmsprop_.register_fake
 def _(param, square_avg, grad, lr, alpha, eps, scale):
+    return None
+
+
+# ---------------------------------------------------------------------------------------------
+# SGD / Adam / AdamW / RMSprop with weight decay, optional grad-norm clipping (in place)
+# ---------------------------------------------------------------------------------------------
+def optim_config(kind: int, nesterov: bool, lr: float, alpha: float, eps: float, momentum: float, beta1: float,
+                 beta2: float, weight_decay: float, max_norm: float, grad_scale: float, skip=()):
+    """f3_optim_config from Python values; skip = flat [lo0, len0, lo1, len1, ...] of the no-gradient ranges."""
+    c = _lib.F3OptimConfig()
+    c.kind, c.nesterov = int(kind), int(bool(nesterov))
+    c.lr, c.alpha, c.eps, c.momentum = lr, alpha, eps, momentum
+    c.beta1, c.beta2, c.weight_decay, c.max_norm, c.grad_scale = beta1, beta2, weight_decay, max_norm, grad_scale
+    if len(skip) % 2 or len(skip) // 2 > _lib.OPT_MAX_SKIP:
+        raise RuntimeError(f"fall3 optim_: at most {_lib.OPT_MAX_SKIP} (lo, len) skip ranges")
+    c.nskip = len(skip) // 2
+    for j in range(c.nskip):
+        c.skip_lo[j], c.skip_len[j] = int(skip[2 * j]), int(skip[2 * j + 1])
+    return c
+
+
+def optim_scalars(device):
+    """A zeroed step-scalar block (f3_optim_scalars_bytes) as an fp32 tensor; see scalar_views."""
+    return torch.zeros(int(lib().f3_optim_scalars_bytes()) // 4, dtype=torch.float32, device=device)
+
+
+def scalar_views(scalars: Tensor):
+    """(t int64[1], bias_correction1, bias_correction2_sqrt, clip_coef, grad_norm: fp32[1] each) views of a
+    step-scalar block, in the layout include/fall3.h documents."""
+    return (scalars[0:2].view(torch.int64), scalars[2:3], scalars[3:4], scalars[4:5], scalars[5:6])
+
+
+@torch.library.custom_op("fall3::optim_", mutates_args=("param", "state0", "state1", "scalars"))
+def optim_(param: Tensor, state0: Tensor, state1: Tensor, scalars: Tensor, grad: Tensor, kind: int, nesterov: bool,
+           lr: float, alpha: float, eps: float, momentum: float, beta1: float, beta2: float, weight_decay: float,
+           max_norm: float, grad_scale: float, skip: List[int]) -> None:
+    """state0 / state1 with no elements stand for "no such state" (SGD without momentum; state1 of
+    every kind but Adam / AdamW)."""
+    for t in (param, state0, state1, grad):
+        if not t.is_contiguous():
+            raise RuntimeError("fall3 optim_: contiguous tensors required")
+    c = optim_config(kind, nesterov, lr, alpha, eps, momentum, beta1, beta2, weight_decay, max_norm, grad_scale, skip)
+    s0 = state0 if state0.numel() else None
+    s1 = state1 if state1.numel() else None
+    check(lib().f3_optim_step(c, ptr(param), ptr(s0), ptr(s1), ptr(grad), param.numel(), ptr(scalars),
+                              stream_handle()), "optim step")
+
+
+@optim_.register_fake
+def _(param, state0, state1, scalars, grad, kind, nesterov, lr, alpha, eps, momentum, beta1, beta2, weight_decay,
+      max_norm, grad_scale, skip):
     return None

@@ -1,4 +1,6 @@
-"""Fused training step: forward -> soft-target CE -> backward -> (all-reduce) -> RMSprop.
+"""Fused training step: forward -> soft-target CE -> backward -> (all-reduce) -> optimizer
+(RMSprop by default; SGD / Adam / AdamW, weight decay and global grad-norm clipping through
+TrainStep(optimizer=..., max_norm=...), model/optimizer.py:8-35, root main.py:108-113).
 
 This is the reference's inner loop body (Multimodal_Fall3/model/main.py:97-132; notebook
 GSTCAN_HAR_conv_10kfold.ipynb:1103-1116) as native calls on one HIP stream with every
@@ -22,7 +24,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from ._lib import check, lib, ptr, stream_handle
+from . import ops, optim as _optim
+from ._lib import ENTRY_PARAM, check, lib, ptr, stream_handle
 
 
 class GradSync:
@@ -93,18 +96,56 @@ def rccl_options():
 class TrainStep:
     """`optimizer` (optional, e.g. fall3 RMSprop driven by a CosineLRScheduler): its
     param_groups[0] lr / alpha / eps are read at every step, so a scheduler's step(epoch) takes
-    effect as with the reference's optimizer.step() (model/main.py:127, 321-322)."""
+    effect as with the reference's optimizer.step() (model/main.py:127, 321-322).
+
+    The optimizer's class picks the update: f3.RMSprop / SGD / Adam / AdamW (or torch.optim's), with the
+    hyper-parameters of its param_groups[0] (momentum, nesterov, betas, weight_decay, ...), also read at
+    every step. `max_norm` (TRAIN.MAX_NORM) clips the global L2 gradient norm as clip_grad_norm_ does
+    (root main.py:108-113): the coefficient is applied inside the update, self.grads stays unscaled, and
+    `grad_norm` / `clip_coef` are 1-element device tensors of the last step (no host sync). RMSprop
+    without weight decay or clipping (the default, and what bench.py measures) runs exactly the
+    launches it always did (f3_net_backward_rmsprop / f3_rmsprop_step); everything else runs
+    f3_net_backward_optim / f3_optim_step. The states live in flat buffers (`square_avg`;
+    `momentum_buffer`; `exp_avg`, `exp_avg_sq`) and the step count on the device (`step_count`), so a
+    captured step advances it; optimizer_state_dict() / load_optimizer_state_dict() convert to and
+    from torch's state_dict layout (model/main.py:302, 336)."""
 
     def __init__(self, model, batch, lr=1e-3, alpha=0.99, eps=1e-8, process_group=None, optimizer=None,
-                 phased=None, force_sync=False):
+                 phased=None, force_sync=False, max_norm=None):
         self.model = model
         self.N = batch
         self.lr, self.alpha, self.eps = lr, alpha, eps
         self.optimizer = optimizer
+        self.max_norm = max_norm
+        self.kind = _optim.optimizer_kind(optimizer) if optimizer is not None else "rmsprop"
         dev = model.flat_parameters().device
         nat = model._native
         self.grads = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
-        self.square_avg = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
+        # flat optimizer states, per kind (state0 / state1 of f3_optim_step)
+        group = self._group()
+        _optim.check_supported(self.kind, group)
+        self._state = {k: torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
+                       for k in _optim.state_keys(self.kind, group)}
+        self.square_avg = self._state.get("square_avg")
+        self.momentum_buffer = self._state.get("momentum_buffer")
+        self.exp_avg, self.exp_avg_sq = self._state.get("exp_avg"), self._state.get("exp_avg_sq")
+        # step scalars (f3_optim_scalars_bytes): device step count, bias corrections, clip coefficient, norm
+        self.scalars = ops.optim_scalars(dev)
+        self.step_count, _, _, self.clip_coef, self.grad_norm = ops.scalar_views(self.scalars)
+        self._legacy_steps = 0  # steps of the plain-RMSprop launches (which keep no device count)
+        self._graph_legacy = False
+        # the entries no backward writes (f3_net_entry_nograd): skipped by every non-RMSprop update
+        h0 = nat.h
+        self._nograd = {name for i, (name, kind, _, _) in enumerate(nat.entries)
+                        if kind == ENTRY_PARAM and lib().f3_net_entry_nograd(h0, i) == 1}
+        self._skip = []
+        for name, shape, off in model.param_views():
+            if name in self._nograd:
+                n4 = (int(np.prod(shape)) + 3) // 4 * 4
+                if self._skip and self._skip[-2] + self._skip[-1] == off:
+                    self._skip[-1] += n4
+                else:
+                    self._skip += [off, n4]
         self.ws = torch.empty(nat.workspace_bytes(batch), dtype=torch.uint8, device=dev)
         self.out = torch.empty(batch, model.spec.num_class, dtype=torch.float32, device=dev)
         self.dout = torch.empty_like(self.out)
@@ -167,11 +208,44 @@ class TrainStep:
         self.forward_loss(skel, sensor, label)
         self.backward_phase(0)
 
-    def optimizer_step(self):
+    # -- optimizer plumbing ------------------------------------------------------
+    def _group(self):
+        """The hyper-parameters in force: the optimizer's param_groups[0], or the constructor's RMSprop values."""
         if self.optimizer is not None:
-            g = self.optimizer.param_groups[0]
+            return self.optimizer.param_groups[0]
+        return {"lr": self.lr, "alpha": self.alpha, "eps": self.eps}
+
+    def _legacy(self, group):
+        """Plain RMSprop (no decay, no clipping): the launches of f3_rmsprop_step / f3_net_backward_rmsprop."""
+        return self.kind == "rmsprop" and not group.get("weight_decay", 0) and not self.max_norm
+
+    def _config(self, group, grad_scale):
+        _optim.check_supported(self.kind, group)
+        keys = _optim.state_keys(self.kind, group)
+        for k in keys:
+            if k not in self._state:  # e.g. a momentum set after construction
+                self._state[k] = torch.zeros_like(self.grads)
+                setattr(self, k, self._state[k])
+        cfg = ops.optim_config(max_norm=float(self.max_norm or 0.0), grad_scale=grad_scale, skip=self._skip,
+                               **_optim.hyper(self.kind, group))
+        st = [self._state[k] for k in keys] + [None, None]
+        return cfg, st[0], st[1]
+
+    def _count_legacy(self):
+        if not torch.cuda.is_current_stream_capturing():
+            self._legacy_steps += 1
+
+    def optimizer_step(self):
+        g = self._group()
+        if self.optimizer is not None:
             self.lr, self.alpha, self.eps = g["lr"], g.get("alpha", self.alpha), g.get("eps", self.eps)
         scale = 1.0 / self.world
+        if not self._legacy(g):
+            cfg, s0, s1 = self._config(g, scale)
+            check(lib().f3_optim_step(cfg, ptr(self.model.flat_parameters()), ptr(s0), ptr(s1), ptr(self.grads),
+                                      self.grads.numel(), ptr(self.scalars), stream_handle()), f"{self.kind} step")
+            return
+        self._count_legacy()
         check(lib().f3_rmsprop_step(ptr(self.model.flat_parameters()), ptr(self.square_avg), ptr(self.grads),
                                     self.grads.numel(), self.lr, self.alpha, self.eps, scale, stream_handle()),
               "rmsprop")
@@ -180,10 +254,19 @@ class TrainStep:
         """loss.backward() + optimizer.step() in one native call (world 1): each skeleton layer's
         RMSprop update starts on the queue that finishes its gradients (f3_net_backward_rmsprop);
         self.grads holds the gradients afterwards as with backward_phase(0)."""
+        g = self._group()
         if self.optimizer is not None:
-            g = self.optimizer.param_groups[0]
             self.lr, self.alpha, self.eps = g["lr"], g.get("alpha", self.alpha), g.get("eps", self.eps)
         m = self.model
+        if not self._legacy(g):
+            # the generalisation (f3_net_backward_optim): per-layer updates of any kind, or with clipping
+            # one flat update after the join (the norm needs every gradient)
+            cfg, s0, s1 = self._config(g, 1.0)
+            check(lib().f3_net_backward_optim(m._native.h, self.N, ptr(m.flat_parameters()), ptr(self.dout),
+                                              ptr(self.grads), ptr(s0), ptr(s1), ptr(self.scalars), ptr(self.ws),
+                                              cfg, stream_handle()), f"fall3 backward + {self.kind}")
+            return
+        self._count_legacy()
         check(lib().f3_net_backward_rmsprop(m._native.h, self.N, ptr(m.flat_parameters()), ptr(self.dout),
                                             ptr(self.grads), ptr(self.square_avg), ptr(self.ws), self.lr, self.alpha,
                                             self.eps, stream_handle()), "fall3 backward + rmsprop")
@@ -220,6 +303,8 @@ class TrainStep:
         if label.data_ptr() != s[2].data_ptr():
             s[2].copy_(label)
         g_head, g_tail, g_opt = self.graph
+        if self._graph_legacy:
+            self._legacy_steps += 1
         g_head.replay()
         if g_tail is not None:
             # the captured phase 1 joined its queues into the capturing stream (net.cpp
@@ -259,4 +344,46 @@ class TrainStep:
         g_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g_opt):
             self.optimizer_step()
+        self._graph_legacy = self._legacy(self._group())
         self.graph = (g_head, g_tail, g_opt)
+
+    # -- checkpoint (model/main.py:302 optimizer.load_state_dict, :336 "optimizer": optimizer.state_dict()) --
+    def _layout(self):
+        """[(shape, flat offset, nograd)] in model.parameters() order."""
+        views = {name: (shape, off) for name, shape, off in self.model.param_views()}
+        return [(tuple(views[n][0]), views[n][1], n in self._nograd) for n, _ in self.model.named_parameters()]
+
+    def steps_taken(self):
+        """Optimizer steps so far (reads the device count: a host sync)."""
+        return int(self.step_count.item()) + self._legacy_steps
+
+    def optimizer_state_dict(self):
+        """torch.optim.<kind>(model.parameters()).state_dict() of this step's optimizer state: loads into
+        torch's optimizer, into f3's, and back into a TrainStep (load_optimizer_state_dict)."""
+        group = self._group()
+        full = _optim.torch_defaults(self.kind)
+        full.update({k: v for k, v in group.items() if k != "params"})
+        keys = _optim.state_keys(self.kind, full)
+        return _optim.flat_to_state_dict(self.kind, full, self._layout(), [self._state[k] for k in keys],
+                                         self.steps_taken())
+
+    def load_optimizer_state_dict(self, sd):
+        """Restore the flat states, the step count and the hyper-parameters from a state_dict written by
+        optimizer_state_dict() or by torch.optim.<kind>(model.parameters()) (in place: a captured graph stays valid,
+        but keeps the hyper-parameters it baked in)."""
+        bufs, step, group = _optim.state_dict_to_flat(self.kind, sd, self._layout(), self.grads.numel(),
+                                                      device=self.grads.device)
+        keys = _optim.state_keys(self.kind, group)
+        for k, b in zip(keys, bufs):
+            if k not in self._state:
+                self._state[k] = torch.zeros_like(self.grads)
+                setattr(self, k, self._state[k])
+            self._state[k].copy_(b)
+        self.step_count.fill_(step)
+        self._legacy_steps = 0
+        hyper = {k: v for k, v in group.items() if k != "params"}
+        if self.optimizer is not None:
+            self.optimizer.param_groups[0].update(hyper)
+        else:
+            self.lr, self.alpha, self.eps = hyper.get("lr", self.lr), hyper.get("alpha", self.alpha), hyper.get(
+                "eps", self.eps)

@@ -12,6 +12,9 @@
  *   f3_rmsprop_step    <- optimizer.step()                model/main.py:127, optimizer.py:21
  *   f3_net_backward_rmsprop <- loss.backward(); optimizer.step()  (one GPU: the update per layer
  *                              as soon as its gradients are final)
+ *   f3_optim_step      <- clip_grad_norm_(); optimizer.step() for torch.optim.SGD / Adam / AdamW /
+ *                         RMSprop with weight decay   model/optimizer.py:20-29, root main.py:108-113
+ *   f3_net_backward_optim <- loss.backward(); clip_grad_norm_(); optimizer.step() in one call
  *
  * Conventions: plain pointers to device memory (HIP), sizes in elements, a HIP stream
  * passed as void*. No call allocates, frees or synchronises: every buffer (flat
@@ -145,6 +148,71 @@ int f3_net_status(f3_net* net, int wait);
  * sq = alpha*sq + (1-alpha)*g^2 ; p -= lr*g/(sqrt(sq)+eps). */
 int f3_rmsprop_step(float* params, float* square_avg, const float* grads, int64_t n, float lr, float alpha,
                     float eps, float grad_scale, void* stream);
+
+/* ---- SGD / Adam / AdamW / RMSprop with weight decay and global grad-norm clipping ----
+ * f3_optim_config  <- the arguments of torch.optim.RMSprop / SGD / Adam / AdamW as build_optimizer
+ *                     passes them (model/optimizer.py:8-29: lr, momentum, betas, eps, weight_decay)
+ *                     plus TRAIN.MAX_NORM (root main.py:108-113 clip_grad_norm_).
+ * Arithmetic is torch.optim's on g = grad_scale * clip_coef * grad:
+ *   RMSPROP  g += wd p; sq = alpha sq + (1-alpha) g^2; p -= lr g / (sqrt(sq) + eps)
+ *   SGD      g += wd p; buf = momentum buf + g; p -= lr (nesterov ? g + momentum buf : buf)
+ *            (dampening 0; a zero buf reproduces torch's first step; momentum 0 keeps no buf)
+ *   ADAM     g += wd p; m += (1-beta1)(g - m); v = beta2 v + (1-beta2) g^2;
+ *            p -= lr/(1-beta1^t) m / (sqrt(v)/sqrt(1-beta2^t) + eps)
+ *   ADAMW    p *= 1 - lr wd, then ADAM with wd = 0
+ * state0 / state1: RMSPROP square_avg / -, SGD momentum_buffer (NULL for momentum 0) / -, ADAM(W)
+ * exp_avg / exp_avg_sq. The state recurrences are evaluated in fp64 and rounded to fp32 once; the
+ * one sqrt and division per element are fp32. Unsupported (F3_EINVAL): RMSprop momentum, nesterov
+ * without momentum, negative / non-finite settings. The elements of skip_lo[i] .. + skip_len[i]
+ * (floats, multiples of 4; the entries no backward writes, f3_net_entry_nograd) are left untouched
+ * in params and states, as torch.optim skips a parameter whose .grad is None. */
+enum { F3_OPT_RMSPROP = 0, F3_OPT_SGD = 1, F3_OPT_ADAM = 2, F3_OPT_ADAMW = 3 };
+#define F3_OPT_MAX_SKIP 4
+typedef struct f3_optim_config {
+  int kind;            /* F3_OPT_*  (OPTIM.TYPE, optimizer.py:20-29) */
+  int nesterov;        /* SGD(nesterov=) */
+  double lr;           /* OPTIM.LR */
+  double alpha;        /* RMSprop(alpha=) */
+  double eps;          /* OPTIM.EPS (RMSprop / Adam / AdamW eps) */
+  double momentum;     /* OPTIM.MOMENTUM (SGD) */
+  double beta1, beta2; /* OPTIM.BETAS */
+  double weight_decay; /* OPTIM.WEIGHT_DECAY */
+  double max_norm;     /* TRAIN.MAX_NORM, clip_grad_norm_(parameters, max_norm) L2; 0 = off */
+  double grad_scale;   /* 1.0 = torch semantics; 1/world after a summed all-reduce */
+  int nskip;           /* <= F3_OPT_MAX_SKIP ranges that never receive a gradient */
+  int64_t skip_lo[F3_OPT_MAX_SKIP], skip_len[F3_OPT_MAX_SKIP];
+} f3_optim_config;
+/* The step scalars: a device block of f3_optim_scalars_bytes() bytes (8-byte aligned, zeroed by the
+ * caller before the first step) that each step's one-workgroup "begin" kernel rewrites and every
+ * update launch of the step reads: int64 t (the step count, incremented per step, so a replayed HIP
+ * graph advances it) at byte 0; fp32 1/(1-beta1^t), 1/sqrt(1-beta2^t) (fp64 from t, rounded once),
+ * clip_coef = min(1, max_norm/(norm + 1e-6)) and grad_norm = grad_scale * ||grads||_2 at bytes 8, 12,
+ * 16, 20 (clip_coef 1, grad_norm 0 with max_norm 0); then the norm's per-workgroup fp64 partial sums,
+ * added in index order (no float atomics: same bits every run). */
+int64_t f3_optim_scalars_bytes(void);
+/* optimizer.step() (model/main.py:127), preceded by clip_grad_norm_ when max_norm > 0 (root
+ * main.py:108-113): [norm partials], begin, one flat update over n floats. grads are not modified
+ * (the clip coefficient is a factor inside the update). F3_OPT_RMSPROP with weight_decay 0 and
+ * max_norm 0 launches f3_rmsprop_step's kernel (same bits). */
+int f3_optim_step(const f3_optim_config* cfg, float* params, float* state0, float* state1, const float* grads,
+                  int64_t n, void* scalars, void* stream);
+/* The same update over nranges <= 8 ranges (offsets / lengths in floats, multiples of 4) of the flat
+ * buffers in one launch, as the per-layer updates inside f3_net_backward_optim issue it; max_norm
+ * must be 0. Elements outside the ranges are untouched. */
+int f3_optim_step_ranges(const f3_optim_config* cfg, float* params, float* state0, float* state1,
+                         const float* grads, int nranges, const int64_t* lo, const int64_t* len, void* scalars,
+                         void* stream);
+/* loss.backward(); [clip_grad_norm_;] optimizer.step() (model/main.py:115-127) in one call: the
+ * generalisation of f3_net_backward_rmsprop. Without clipping the begin kernel runs before the
+ * private queues fork and each skeleton layer's update is issued on the queue that finishes its
+ * gradients; with clipping (the norm needs every gradient) one flat update follows the join. The
+ * net's no-gradient entries are skipped (cfg's own skip list is ignored). */
+int f3_net_backward_optim(f3_net* net, int batch, float* params, const float* dout, float* grads, float* state0,
+                          float* state1, void* scalars, void* workspace, const f3_optim_config* cfg, void* stream);
+/* 1 if entry i is a parameter no backward ever writes (its .grad stays None in the reference: the
+ * CNN1D's unused fc, GSTCAN_UR_conv.ipynb:493-514), so torch.optim keeps no state for it and applies
+ * no decay; 0 otherwise; -1 for a bad index. */
+int f3_net_entry_nograd(const f3_net* net, int i);
 
 /* Kernel-level entries used by the unit tests and bench.py: out[N,T_out,V,Cout] = conv_(KT,1)(x)
  * with x [N,T_in,V,Cin] channels-last, w in reference layout [Cout][Cin][KT], bias [Cout]
