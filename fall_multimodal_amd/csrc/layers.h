@@ -68,6 +68,20 @@ struct GcnDgradMixArgs {
                              // the same frames and sum to the same bits; tests pass a few
 };
 
+// bf16x3: the graph mix fused into the gcn forward GEMM (gcn_fwd.hip); Z is written, never read back
+struct GcnFwdMixArgs {
+  int frames, K, V, Cin, C;
+  const float* A;             // A_eff [K][V][V]
+  const float* x;             // fp32 [frames][V][Cin]
+  unsigned short* z3;         // out: [frames * V] rows [z_hi | z_lo] of 2 K Cin bf16 (MixArgs::z3)
+  const unsigned short* w;    // packed split gcn weight [C][2 K Cin] (prep code 4)
+  const float* bias;          // graph-mixed bias [V][C]
+  float* g;                   // out: fp32 [frames * V][C]
+  double* st_sum;             // BN1 sums [C], added to
+  double* st_sq;
+  const unsigned short* zero; // zero page (16 B are read)
+};
+
 // the first block's graph convolution (Cin <= 4, C = 64) in the bf16 mode (layer0.hip)
 struct Gcn0Args {
   int frames, K, V, Ci;
@@ -250,6 +264,8 @@ int f3_mix_bwd_parts(const f3::MixArgs* a);  // dA partial rows the LDS mix back
 bool f3_gcn_dgrad_mix_ok(int K, int V, int Cin, int C);  // shapes gcn_bwd.hip covers
 int f3_gcn_dgrad_mix(const f3::GcnDgradMixArgs* a, hipStream_t s);
 int f3_gcn_dgrad_mix_parts(const f3::GcnDgradMixArgs* a);  // dA partial rows the launch leaves
+bool f3_gcn_fwd_mix_ok(int K, int V, int Cin, int C);  // shapes gcn_fwd.hip covers
+int f3_gcn_fwd_mix(const f3::GcnFwdMixArgs* a, hipStream_t s);
 bool f3_mix_lds_ok(int K, int V, int Cin);  // the LDS/MFMA mix path (takes bf16 dZ)
 bool f3_mix_x3_ok(int K, int V, int Cin);   // the split-bf16 mix kernels (bf16x3 mode; MixArgs::z3)
 int f3_split_x3(const float* x, unsigned short* out, long long rows, int C, hipStream_t s);  // [hi | lo] rows

@@ -596,6 +596,13 @@ inline bool gcn_dgrad_fused() {
   return on;
 }
 
+// F3_GCN_FWD_FUSED=0: the graph mix and the gcn forward GEMM as two kernels through the Z rows in HBM
+// (the A/B baseline of gcn_fwd.hip's fused kernel); read once per process
+inline bool gcn_fwd_fused() {
+  static const bool on = !getenv("F3_GCN_FWD_FUSED") || atoi(getenv("F3_GCN_FWD_FUSED")) != 0;
+  return on;
+}
+
 // prep code of the packed GEMM weights: 0 fp32, 1 bf16, 2 split hi / lo planes
 inline int wcode(const f3_net& n) { return n.cfg.precision == F3_PRECISION_BF16 ? 1 : is_x3(n) ? 2 : 0; }
 // bf16 view of an activation slot (bf16 mode stores GEMM operand tensors as bf16)
@@ -686,6 +693,15 @@ int stream_forward_layer(const f3_net& net, int si, int N, int train, const Ptrs
       g0.z = bfa(X.z, 1); g0.g = bfa(X.g, 1); g0.st_sum = X.bn1.fsum; g0.st_sq = X.bn1.fsq;
       g0.f32 = x3;  // bf16x3: fp32 x / w / Z / g behind the same pointers
       F3_TRY(f3_gcn0_fwd(&g0, s));
+    } else if (x3 && f3_mix_x3_ok(K, V, Ci) && Ci == 64 && K * Ci == 192 && V <= 18 && (C == 64 || C == 128) &&
+               gcn_fwd_fused() && f3_gcn_fwd_mix_ok(K, V, Ci, C)) {
+      // layers 1-3: the mix computed into the GEMM's A blocks (gcn_fwd.hip), same bits as the pair below
+      GcnFwdMixArgs gf;
+      std::memset(&gf, 0, sizeof(gf));
+      gf.frames = N * Ti; gf.K = K; gf.V = V; gf.Cin = Ci; gf.C = C; gf.A = X.aeff; gf.x = X.x;
+      gf.z3 = bfa(X.z, 1); gf.w = bf(X.gw, 1); gf.bias = X.beff; gf.g = X.g;
+      gf.st_sum = X.bn1.fsum; gf.st_sq = X.bn1.fsq; gf.zero = w.zero;
+      F3_TRY(f3_gcn_fwd_mix(&gf, s));
     } else {
       MixArgs mx;
       std::memset(&mx, 0, sizeof(mx));
@@ -2062,6 +2078,27 @@ int f3_gcn_dgrad_mix_x3(const void* dg3, const float* w, void* wpack, const floa
   a.w = static_cast<const unsigned short*>(wpack); a.A = A_eff; a.x = x; a.dx = dx; a.dA = dA;
   a.accumulate = accumulate != 0; a.part = part; a.max_workgroups = max_workgroups;
   return f3_gcn_dgrad_mix(&a, s);
+}
+
+int f3_gcn_fwd_mix_x3(const float* A_eff, const float* x, const float* w, void* wpack, const float* bias_v, void* z3,
+                      float* g, double* st_sum, double* st_sq, int frames, int K, int V, int Cin, int C,
+                      void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!A_eff || !x || !wpack || !bias_v || !z3 || !g || !st_sum || !st_sq || frames < 0) return F3_EINVAL;
+  if (!f3_gcn_fwd_mix_ok(K, V, Cin, C)) return F3_EINVAL;
+  if (w) {  // the step's packing of w [C][K Cin] (w == NULL: wpack already packed)
+    PrepTable t;
+    t.n = 0;
+    add_job(t, PREP_PACK_CONV, C * K * Cin * x3mul(x3code()), static_cast<float*>(wpack), w, nullptr, nullptr, C,
+            K * Cin, 1, x3code());
+    F3_TRY(f3_prep(t, s));
+  }
+  GcnFwdMixArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.frames = frames; a.K = K; a.V = V; a.Cin = Cin; a.C = C; a.A = A_eff; a.x = x;
+  a.z3 = static_cast<unsigned short*>(z3); a.w = static_cast<const unsigned short*>(wpack); a.bias = bias_v; a.g = g;
+  a.st_sum = st_sum; a.st_sq = st_sq; a.zero = test_zero_page();
+  return f3_gcn_fwd_mix(&a, s);
 }
 
 // debug accessor (tests/tools only): device pointer of a named per-layer workspace tensor

@@ -323,6 +323,15 @@ int f3_graph_mix_backward_ex(const float* A_eff, const void* x, const void* dz, 
 int f3_gcn_dgrad_mix_x3(const void* dg3, const float* w, void* wpack, const float* A_eff, const float* x, float* dx,
                         float* dA, int frames, int K, int V, int Cin, int C, int accumulate, int max_workgroups,
                         void* stream);
+/* bf16x3 step: the graph mix fused into the gcn forward 1x1 GEMM, as stream_forward launches it (one
+ * kernel instead of f3_graph_mix_forward_ex(F3_MIX_X3 | F3_MIX_Z3) + f3_conv_step_x3cat(F3_STEP_GCN_FWD);
+ * same bits). x fp32 [frames][V][Cin]; w [C][K Cin] is packed into wpack (2 C K Cin bf16) when non-NULL;
+ * bias_v [V][C]. Outputs: z3 rows [z_hi | z_lo] of 2 K Cin bf16 per (frame, node), g fp32 [frames V][C];
+ * st_sum / st_sq [C] are added to. F3_EINVAL (nothing written) outside K = 3, Cin = 64, V <= 18,
+ * C in {64, 128}. (F3_GCN_FWD_FUSED=0 makes the step launch the pair; this entry always runs the kernel.) */
+int f3_gcn_fwd_mix_x3(const float* A_eff, const float* x, const float* w, void* wpack, const float* bias_v, void* z3,
+                      float* g, double* st_sum, double* st_sq, int frames, int K, int V, int Cin, int C,
+                      void* stream);
 
 const char* f3_status_string(int status);
 
