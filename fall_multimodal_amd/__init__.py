@@ -11,7 +11,8 @@ plus TrainStep, the fused multi-stream step used by bench.py, the skeleton-only 
 SkeletonTransformer (BASELINE config 5: skeleton_transformer.py) with SktrStep, musa.Model (the model
 the root Multimodal_Fall3/main.py trains: musa_model.py) with musa.MusaStep, and the steps either side of it
 (SURVEY §8f): data (window files, video-wise splits, pinned double-buffered loader) and
-evaluate (valid / test loops, top-k, macro P/R/F1, best-model checkpoints).
+evaluate (valid / test loops, top-k, macro P/R/F1, best-model checkpoints), and metrics (StepMetrics:
+loss, top-k and confusion counts accumulated on the device, per step or per eval pass, without a sync).
 """
 from .config import CfgNode, get_cfg_defaults
 from .graph import Graph
@@ -22,8 +23,10 @@ from .train import TrainStep
 from .targcn import TARGCN, TargcnStep
 from .sktr import SkeletonTransformer, SktrStep
 from . import musa
-from . import data, evaluate
+from . import data, evaluate, metrics
+from .metrics import StepMetrics, summarize
 
 __all__ = ["build_model", "build_optimizer", "get_cfg_defaults", "CfgNode", "Graph", "Fall3Net", "NetSpec",
            "STGCAN", "BiLSTM", "CNN_BiLSTM", "TwoStreamSTGCAN", "TwoStreamSTGCAN_BiLSTM", "TwoStreamSpatialTemporalGraph",
-           "RMSprop", "SGD", "Adam", "AdamW", "TrainStep", "TARGCN", "TargcnStep", "SkeletonTransformer", "SktrStep", "musa", "data", "evaluate"]
+           "RMSprop", "SGD", "Adam", "AdamW", "TrainStep", "TARGCN", "TargcnStep", "SkeletonTransformer", "SktrStep", "musa", "data", "evaluate",
+           "metrics", "StepMetrics", "summarize"]

@@ -34,12 +34,14 @@ EXPORTS = (
     "f3_musa_guards",
     "f3_dwconv_t_forward", "f3_pointwise_conv", "f3_rgb_scratch_floats", "f3_rgb_forward", "f3_rgb_backward",
     "f3_optim_scalars_bytes", "f3_optim_step", "f3_optim_step_ranges", "f3_net_backward_optim", "f3_net_entry_nograd",
+    "f3_metrics_bytes", "f3_metrics_reset", "f3_metrics_update", "f3_segment_norms_scratch_bytes", "f3_segment_norms",
 )
 
 F3_OK, F3_EINVAL, F3_EBATCH, F3_EHIP, F3_ESTATE, F3_EDEVICE = 0, 1001, 1002, 1003, 1004, 1005
 ENTRY_PARAM, ENTRY_BUFFER, ENTRY_COUNTER = 0, 1, 2
 OPT_RMSPROP, OPT_SGD, OPT_ADAM, OPT_ADAMW = 0, 1, 2, 3
 OPT_MAX_SKIP = 4
+METRICS_MAXK, METRICS_MAXC = 8, 64
 
 
 class F3OptimConfig(ctypes.Structure):
@@ -107,6 +109,11 @@ def lib():
                                      ctypes.POINTER(I64), P, P]),
         "f3_net_backward_optim": (I, [P, I, P, P, P, P, P, P, P, ctypes.POINTER(F3OptimConfig), P]),
         "f3_net_entry_nograd": (I, [P, I]),
+        "f3_metrics_bytes": (I64, [I]),
+        "f3_metrics_reset": (I, [P, I, P]),
+        "f3_metrics_update": (I, [P, P, P, P, P, I, I, ctypes.POINTER(I), I, P]),
+        "f3_segment_norms_scratch_bytes": (I64, [I64, I]),
+        "f3_segment_norms": (I, [P, P, P, I, P, P, I64, ctypes.c_double, P]),
         "f3_conv_forward": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
         "f3_status_string": (ctypes.c_char_p, [I]),
         "f3_net_debug_tensor": (P, [P, I, P, I, I, ctypes.c_char_p]),

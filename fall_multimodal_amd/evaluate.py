@@ -98,6 +98,46 @@ def test(model, loader, loss_fn=None, top_k=(1, 5), num_classes: int | None = No
     return res
 
 
+def _device_pass(model, loader, top_k):
+    """One eval-mode pass whose loss, top-k and confusion counts stay on the device
+    (metrics.StepMetrics, loss computed by the update itself): nothing is concatenated, no
+    per-batch .item(); the one copy to the host is result()'s."""
+    from .metrics import StepMetrics
+    was_training = model.training
+    model.eval()
+    acc = None
+    try:
+        for skel, sensor, label in loader:
+            out = model(skel, sensor)
+            if acc is None:
+                acc = StepMetrics(out.shape[1], top_k, device=out.device)
+            label = label.to(out.device)
+            label = label.long() if label.dim() == 1 else label.float()
+            acc.update(out, label.contiguous())
+    finally:
+        if was_training:
+            model.train()
+    if acc is None:
+        raise ValueError("evaluate: the loader gave no batch")
+    return acc.result()
+
+
+@torch.no_grad()
+def valid_device(model, loader, top_k=(1, 5)):
+    """valid() (model/main.py:148-197) with the metrics accumulated on the device: the same mean of
+    per-batch mean losses (soft-target CE of the module output) and top-k over all rows."""
+    res = _device_pass(model, loader, top_k)
+    return {"loss": res["loss"], "top_k": res["top_k"]}
+
+
+@torch.no_grad()
+def test_device(model, loader, top_k=(1, 5)):
+    """test() (model/main.py:199-245, main_cross_validation.py:247) with the metrics accumulated on the
+    device: the keys and values of test() except the sklearn text `report`."""
+    res = _device_pass(model, loader, top_k)
+    return {k: res[k] for k in ("loss", "top_k", "precision", "recall", "f1", "specificity", "confusion")}
+
+
 def save_best(model, path):
     """Best-model checkpoint in the reference's format (model/main.py:323-328): the keys of
     model.state_dict() are the reference's, so the file loads into either implementation."""

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import ops, optim as _optim
+from . import metrics as _metrics, ops, optim as _optim
 from ._lib import ENTRY_PARAM, check, lib, ptr, stream_handle
 
 
@@ -108,10 +108,16 @@ class TrainStep:
     f3_net_backward_optim / f3_optim_step. The states live in flat buffers (`square_avg`;
     `momentum_buffer`; `exp_avg`, `exp_avg_sq`) and the step count on the device (`step_count`), so a
     captured step advances it; optimizer_state_dict() / load_optimizer_state_dict() convert to and
-    from torch's state_dict layout (model/main.py:302, 336)."""
+    from torch's state_dict layout (model/main.py:302, 336).
+
+    `metrics` (a metrics.StepMetrics, or True for one with top_k=(1,)): every step adds its batch's loss,
+    top-k hits and confusion counts to the device accumulators with one launch directly after the loss
+    (model/main.py:134-135 without the copy to the host), eager or replayed; capture() leaves them as
+    they were. None (the default) issues exactly the launches the step always issued.
+    param_grad_norms() gives the per-parameter gradient norms of model/main.py:84-89 without a sync."""
 
     def __init__(self, model, batch, lr=1e-3, alpha=0.99, eps=1e-8, process_group=None, optimizer=None,
-                 phased=None, force_sync=False, max_norm=None):
+                 phased=None, force_sync=False, max_norm=None, metrics=None):
         self.model = model
         self.N = batch
         self.lr, self.alpha, self.eps = lr, alpha, eps
@@ -150,6 +156,13 @@ class TrainStep:
         self.out = torch.empty(batch, model.spec.num_class, dtype=torch.float32, device=dev)
         self.dout = torch.empty_like(self.out)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        if metrics is True:
+            metrics = _metrics.StepMetrics(model.spec.num_class, top_k=(1,), device=dev)
+        if metrics is not None and (not isinstance(metrics, _metrics.StepMetrics)
+                                    or metrics.num_class != model.spec.num_class or metrics.device != dev):
+            raise ValueError(f"TrainStep: metrics must be a StepMetrics for {model.spec.num_class} classes on {dev}")
+        self.metrics = metrics
+        self._grad_norms = None
         self.pg = process_group
         h = nat.h
         self.sync = GradSync(self.grads, lib().f3_net_grad_split(h), process_group,
@@ -197,6 +210,8 @@ class TrainStep:
         m.native_forward(skel, sensor, self.out, self.ws, True, st)
         check(L.f3_net_loss(m._native.h, self.N, ptr(self.out), ptr(label), ptr(self.loss), ptr(self.dout), st),
               "fall3 loss")
+        if self.metrics is not None:
+            self.metrics.update(self.out, label, self.loss)
 
     def backward_phase(self, phase):
         m = self.model
@@ -322,12 +337,15 @@ class TrainStep:
         world > 1: [fwd+loss+bwd phase 1], [bwd phase 2], [RMSprop], with the two all-reduce
         buckets issued between replays."""
         self._static = (skel, sensor, label)
+        kept = self.metrics.snapshot() if self.metrics is not None else None  # the warm-up steps must not count
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
                 self.forward_backward(skel, sensor, label)
         torch.cuda.current_stream().wait_stream(side)
+        if kept is not None:
+            self.metrics.restore(kept)
         torch.cuda.synchronize()
         g_head = torch.cuda.CUDAGraph()
         g_tail = None
@@ -346,6 +364,21 @@ class TrainStep:
             self.optimizer_step()
         self._graph_legacy = self._legacy(self._group())
         self.graph = (g_head, g_tail, g_opt)
+
+    # -- reporting -----------------------------------------------------------------
+    def param_grad_norms(self):
+        """(names, norms): names in model.named_parameters() order; norms a device fp32 tensor of
+        len(names) + 1 values, the L2 norm of each parameter's gradient and then of all of them, of the
+        gradient the last update consumed (self.grads times 1/world). Two launches, no sync (the
+        reference's visualize_weights_and_gradients calls .item() per parameter, model/main.py:84-89).
+        The same tensor is returned by every call: clone it to keep a step's values."""
+        if self._grad_norms is None:
+            views = {name: (shape, off) for name, shape, off in self.model.param_views()}
+            names = [n for n, _ in self.model.named_parameters()]
+            self._grad_norms = (names, _metrics.SegmentNorms(self.grads, [views[n][1] for n in names],
+                                                             [int(np.prod(views[n][0])) for n in names]))
+        names, seg = self._grad_norms
+        return list(names), seg(1.0 / self.world)
 
     # -- checkpoint (model/main.py:302 optimizer.load_state_dict, :336 "optimizer": optimizer.state_dict()) --
     def _layout(self):

@@ -15,6 +15,9 @@
  *   f3_optim_step      <- clip_grad_norm_(); optimizer.step() for torch.optim.SGD / Adam / AdamW /
  *                         RMSprop with weight decay   model/optimizer.py:20-29, root main.py:108-113
  *   f3_net_backward_optim <- loss.backward(); clip_grad_norm_(); optimizer.step() in one call
+ *   f3_metrics_update  <- cal_top_k_accuracy(), running loss, confusion matrix   model/main.py:57-77,
+ *                         134-135, 189-200 (accumulated on the device: no copy or sync per batch)
+ *   f3_segment_norms   <- param.grad.norm().item() per parameter   model/main.py:84-89
  *
  * Conventions: plain pointers to device memory (HIP), sizes in elements, a HIP stream
  * passed as void*. No call allocates, frees or synchronises: every buffer (flat
@@ -213,6 +216,54 @@ int f3_net_backward_optim(f3_net* net, int batch, float* params, const float* do
  * CNN1D's unused fc, GSTCAN_UR_conv.ipynb:493-514), so torch.optim keeps no state for it and applies
  * no decay; 0 otherwise; -1 for a bad index. */
 int f3_net_entry_nograd(const f3_net* net, int i);
+
+/* ---- step metrics accumulated on the device (no host sync per batch) ----
+ * The accumulator block: device memory of f3_metrics_bytes(C) bytes, 8-byte aligned, zeroed by
+ * f3_metrics_reset:
+ *   byte 0                fp64   loss_sum          sum of per-batch mean losses
+ *   byte 8                int64  batches           number of updates
+ *   byte 16               int64  rows              number of rows seen
+ *   byte 24               int64  correct[F3_METRICS_MAXK]   one counter per requested k (the rest stay 0)
+ *   byte 24 + 8 MAXK      int64  confusion[C*C]    row = true class, column = predicted class
+ * True class of a row: arg-max of its soft label (lowest index on a tie), or label_idx. Predicted
+ * class: arg-max of out by the same rule. Rank of the target t: the number of classes c with
+ * out[c] > out[t], or out[c] == out[t] and c < t; a NaN logit orders above every number and ties with
+ * another NaN (torch.topk's order). correct[j] counts the rows with rank < top_k[j]. One 256-thread
+ * workgroup per update, integer counts gathered in LDS, every word of the block written by one
+ * thread with plain loads and stores (updates on one stream are serial), the loss reduced in a fixed
+ * order: the same inputs give the same bits on every run. No call allocates or reads back to the
+ * host, so all of them can be captured into a HIP graph. */
+#define F3_METRICS_MAXK 8
+/* Size of the block for C classes (1 <= C <= 64: the confusion tile is held in LDS); 0 for a bad C. */
+int64_t f3_metrics_bytes(int C);
+/* Zero the block (the start of an epoch, or of model/main.py:148 valid() / :199 test()). */
+int f3_metrics_reset(void* acc, int C, void* stream);
+/* Add one batch: replaces cal_top_k_accuracy(output, target, top_k) and the running loss of
+ * model/main.py:134-135 (which begin with a copy to the host), and the concatenation of every batch's
+ * logits behind the confusion matrix and macro P/R/F1 of model/main.py:189-200, 230-245. out
+ * f32[N,C] is the module output. Exactly one of label (f32[N,C], soft or one-hot) and label_idx
+ * (i64[N]; an index outside [0,C) counts in rows only) is given. loss != NULL: the batch mean that
+ * f3_net_loss / f3_soft_ce wrote, added as (double)*loss. loss == NULL (the eval path):
+ * -(1/N) sum_i sum_c y_ic log_softmax(out_i)_c is computed with ce_kernel's row arithmetic, an
+ * index label taken as one-hot. top_k: nk <= F3_METRICS_MAXK host ints, passed to the kernel by
+ * value. F3_EINVAL: N < 1, C < 1, C > 64, nk > F3_METRICS_MAXK, a k < 1 or k > C, both or neither
+ * label forms. */
+int f3_metrics_update(void* acc, const float* out, const float* label, const int64_t* label_idx, const float* loss,
+                      int N, int C, const int* top_k, int nk, void* stream);
+/* Per-tensor gradient L2 norms: replaces the param.grad.norm().item() per parameter of
+ * visualize_weights_and_gradients (model/main.py:84-89). norms[s] = scale * ||g[seg_off[s] :
+ * seg_off[s] + seg_len[s]]||_2 for s < nseg, norms[nseg] the same over all segments together.
+ * seg_off / seg_len: device int64 tables in floats; offsets are multiples of 4 (g 16-byte aligned),
+ * lengths arbitrary including 0; elements between segments are never read. Two launches: a
+ * workgroup per 8192-float chunk of one segment stores an fp64 partial (an fp32 square is exact in
+ * fp64; no float atomics); one workgroup then adds each segment's partials in index order and the
+ * segment sums in a fixed order, takes sqrt and scale in fp64 and rounds to fp32 once. scratch: 8-byte
+ * aligned device memory of f3_segment_norms_scratch_bytes(sum of lengths, nseg) bytes; the first
+ * launch runs one workgroup per 8 bytes of it. A table needing more partials than the scratch holds
+ * gives NaN norms, never a read past it. */
+int64_t f3_segment_norms_scratch_bytes(int64_t total_len, int nseg);
+int f3_segment_norms(const float* g, const int64_t* seg_off, const int64_t* seg_len, int nseg, float* norms,
+                     void* scratch, int64_t scratch_bytes, double scale, void* stream);
 
 /* Kernel-level entries used by the unit tests and bench.py: out[N,T_out,V,Cout] = conv_(KT,1)(x)
  * with x [N,T_in,V,Cin] channels-last, w in reference layout [Cout][Cin][KT], bias [Cout]
