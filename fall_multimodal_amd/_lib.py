@@ -35,6 +35,7 @@ EXPORTS = (
     "f3_dwconv_t_forward", "f3_pointwise_conv", "f3_rgb_scratch_floats", "f3_rgb_forward", "f3_rgb_backward",
     "f3_optim_scalars_bytes", "f3_optim_step", "f3_optim_step_ranges", "f3_net_backward_optim", "f3_net_entry_nograd",
     "f3_metrics_bytes", "f3_metrics_reset", "f3_metrics_update", "f3_segment_norms_scratch_bytes", "f3_segment_norms",
+    "f3_soft_ce_ex", "f3_net_loss_ex", "f3_grad_accumulate",
 )
 
 F3_OK, F3_EINVAL, F3_EBATCH, F3_EHIP, F3_ESTATE, F3_EDEVICE = 0, 1001, 1002, 1003, 1004, 1005
@@ -114,6 +115,9 @@ def lib():
         "f3_metrics_update": (I, [P, P, P, P, P, I, I, ctypes.POINTER(I), I, P]),
         "f3_segment_norms_scratch_bytes": (I64, [I64, I]),
         "f3_segment_norms": (I, [P, P, P, I, P, P, I64, ctypes.c_double, P]),
+        "f3_soft_ce_ex": (I, [P, P, P, I, I, F, P, P, P]),
+        "f3_net_loss_ex": (I, [P, I, P, P, F, P, P, P]),
+        "f3_grad_accumulate": (I, [P, P, I64, P, P]),
         "f3_conv_forward": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
         "f3_status_string": (ctypes.c_char_p, [I]),
         "f3_net_debug_tensor": (P, [P, I, P, I, I, ctypes.c_char_p]),

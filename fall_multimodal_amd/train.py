@@ -93,6 +93,34 @@ def rccl_options():
     return o
 
 
+def check_step_args(label_smoothing=0.0, accum_iter=1):
+    """TrainStep's checks of its two loop settings (no device needed): label_smoothing a number in
+    [0, 1] (torch.nn.CrossEntropyLoss's range), accum_iter an integer >= 1. Returns (float, int)."""
+    if isinstance(label_smoothing, bool) or not isinstance(label_smoothing, (int, float, np.integer, np.floating)):
+        raise ValueError(f"TrainStep: label_smoothing must be a number in [0, 1], got {label_smoothing!r}")
+    if not 0.0 <= float(label_smoothing) <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError(f"TrainStep: label_smoothing must be in [0, 1], got {label_smoothing!r}")
+    if isinstance(accum_iter, bool) or not isinstance(accum_iter, (int, np.integer)) or accum_iter < 1:
+        raise ValueError(f"TrainStep: accum_iter must be an integer >= 1, got {accum_iter!r}")
+    return float(label_smoothing), int(accum_iter)
+
+
+def accum_updates(num_batches, accum_iter):
+    """Which batches of an epoch end with optimizer.step() and model.zero_grad(): the reference's
+    test `i % accum_iter == 0 or i + 1 == len(dataloader)` with i counted from the epoch's start
+    (model/main.py:115-132). So batch 0 updates alone, then every accum_iter-th batch, then the last."""
+    _, k = check_step_args(0.0, accum_iter)
+    n = int(num_batches)
+    return [i % k == 0 or i + 1 == n for i in range(n)]
+
+
+def step_kwargs(config):
+    """TrainStep's keyword arguments that the reference's loop reads from TRAIN.* (model/main.py:280
+    LABEL_SMOOTHING, :115-132 ACCUM_ITER; root main.py:108-113 MAX_NORM)."""
+    t = config.TRAIN
+    return {"max_norm": t.MAX_NORM, "label_smoothing": t.LABEL_SMOOTHING, "accum_iter": t.ACCUM_ITER}
+
+
 class TrainStep:
     """`optimizer` (optional, e.g. fall3 RMSprop driven by a CosineLRScheduler): its
     param_groups[0] lr / alpha / eps are read at every step, so a scheduler's step(epoch) takes
@@ -114,10 +142,29 @@ class TrainStep:
     top-k hits and confusion counts to the device accumulators with one launch directly after the loss
     (model/main.py:134-135 without the copy to the host), eager or replayed; capture() leaves them as
     they were. None (the default) issues exactly the launches the step always issued.
-    param_grad_norms() gives the per-parameter gradient norms of model/main.py:84-89 without a sync."""
+    param_grad_norms() gives the per-parameter gradient norms of model/main.py:84-89 without a sync.
+
+    `label_smoothing` (TRAIN.LABEL_SMOOTHING, model/main.py:280): above 0 the loss launch is
+    f3_net_loss_ex; `loss`, `dout` and the metrics' loss are the smoothed ones (the reference logs the
+    smoothed loss), ranks and confusion counts come from the unsmoothed label. At 0.0 (the default) the
+    step issues f3_net_loss as ever.
+
+    `accum_iter` (TRAIN.ACCUM_ITER, model/main.py:115-132): above 1 every call runs forward, loss and the
+    whole backward into `grads`, then adds `grads` into the flat `accum` (f3_grad_accumulate; the first
+    micro-batch after an update overwrites), and only update calls all-reduce `accum` and run the flat
+    optimizer update on it, whatever the optimizer, with weight decay and clipping; `grad_norm` and
+    `clip_coef` are those of the accumulated gradient, and p.grad / param_grad_norms() show `accum`.
+    Which calls update follows the reference's rule (accum_updates) from begin_epoch(num_batches) on, or
+    `update=True / False` per call; `pending` counts the micro-batches in `accum`, zero_grad() discards
+    them. steps_taken() and the checkpoint count updates. At 1 (the default) nothing changes: no `accum`,
+    the same launches, the per-layer fused update included."""
 
     def __init__(self, model, batch, lr=1e-3, alpha=0.99, eps=1e-8, process_group=None, optimizer=None,
-                 phased=None, force_sync=False, max_norm=None, metrics=None):
+                 phased=None, force_sync=False, max_norm=None, metrics=None, label_smoothing=0.0, accum_iter=1):
+        self.label_smoothing, self.accum_iter = check_step_args(label_smoothing, accum_iter)
+        if self.accum_iter > 1 and phased:
+            raise ValueError("TrainStep: an accumulating step runs the whole backward per micro-batch (phased=True "
+                             "overlaps an all-reduce that only update calls issue)")
         self.model = model
         self.N = batch
         self.lr, self.alpha, self.eps = lr, alpha, eps
@@ -165,20 +212,38 @@ class TrainStep:
         self._grad_norms = None
         self.pg = process_group
         h = nat.h
-        self.sync = GradSync(self.grads, lib().f3_net_grad_split(h), process_group,
-                             wait_phase1=lambda st: check(lib().f3_net_wait_phase1(h, st), "wait phase 1"),
-                             force=force_sync)
+        # accumulation (accum_iter > 1): the flat accumulator, the device word that makes the next
+        # micro-batch overwrite it (set = model.zero_grad() has run), the position in the epoch
+        self.accum = None
+        self.pending = 0
+        self._i, self._num_batches = 0, None
+        if self.accum_iter > 1:
+            self.accum = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
+            self._accum_reset = torch.ones(1, dtype=torch.int32, device=dev)
+        # the gradient the update, the all-reduce and the reports consume
+        self._gsrc = self.grads if self.accum is None else self.accum
+        if self.accum is None:
+            self.sync = GradSync(self.grads, lib().f3_net_grad_split(h), process_group,
+                                 wait_phase1=lambda st: check(lib().f3_net_wait_phase1(h, st), "wait phase 1"),
+                                 force=force_sync)
+        else:
+            # issued after the accumulate launch on the caller's stream, on update calls only (the other
+            # calls issue no collective: the saving of DDP's no_sync); not overlapped with the backward
+            self.sync = GradSync(self.accum, lib().f3_net_grad_split(h), process_group, force=force_sync)
         self.world = self.sync.world
         # phased=True runs the two-phase backward even on one rank (times its cost against phase 0);
         # force_sync=True (tests) also issues the two all-reduce buckets at world 1
         self.phased = (self.world > 1 or force_sync) if phased is None else bool(phased)
+        if self.accum is not None:
+            self.phased = False
         # expose the flat gradient through the usual .grad attributes
         for (name, shape, off), p in zip(model.param_views(), model.parameters()):
-            p.grad = self.grads[off:off + int(np.prod(shape))].view(shape)
+            p.grad = self._gsrc[off:off + int(np.prod(shape))].view(shape)
         self.graph = None
         self._static = None
         # world 1: the RMSprop update per layer inside the backward (F3_FUSED_OPT=0: one launch after it)
-        self.fused_optimizer = not self.sync.active and os.environ.get("F3_FUSED_OPT", "1") != "0"
+        self.fused_optimizer = (not self.sync.active and self.accum is None
+                                and os.environ.get("F3_FUSED_OPT", "1") != "0")
 
     # -- the pieces ------------------------------------------------------------
     def prepare(self, skel, sensor, label):
@@ -208,8 +273,12 @@ class TrainStep:
         st = stream_handle()
         m = self.model
         m.native_forward(skel, sensor, self.out, self.ws, True, st)
-        check(L.f3_net_loss(m._native.h, self.N, ptr(self.out), ptr(label), ptr(self.loss), ptr(self.dout), st),
-              "fall3 loss")
+        if self.label_smoothing > 0.0:
+            check(L.f3_net_loss_ex(m._native.h, self.N, ptr(self.out), ptr(label), self.label_smoothing,
+                                   ptr(self.loss), ptr(self.dout), st), "fall3 smoothed loss")
+        else:
+            check(L.f3_net_loss(m._native.h, self.N, ptr(self.out), ptr(label), ptr(self.loss), ptr(self.dout), st),
+                  "fall3 loss")
         if self.metrics is not None:
             self.metrics.update(self.out, label, self.loss)
 
@@ -251,19 +320,54 @@ class TrainStep:
             self._legacy_steps += 1
 
     def optimizer_step(self):
+        """The flat update on `grads`, or on `accum` in an accumulating step, which then also sets the
+        reset word (the model.zero_grad() of model/main.py:132: the next micro-batch overwrites)."""
         g = self._group()
         if self.optimizer is not None:
             self.lr, self.alpha, self.eps = g["lr"], g.get("alpha", self.alpha), g.get("eps", self.eps)
         scale = 1.0 / self.world
+        src = self._gsrc
         if not self._legacy(g):
             cfg, s0, s1 = self._config(g, scale)
-            check(lib().f3_optim_step(cfg, ptr(self.model.flat_parameters()), ptr(s0), ptr(s1), ptr(self.grads),
-                                      self.grads.numel(), ptr(self.scalars), stream_handle()), f"{self.kind} step")
-            return
-        self._count_legacy()
-        check(lib().f3_rmsprop_step(ptr(self.model.flat_parameters()), ptr(self.square_avg), ptr(self.grads),
-                                    self.grads.numel(), self.lr, self.alpha, self.eps, scale, stream_handle()),
-              "rmsprop")
+            check(lib().f3_optim_step(cfg, ptr(self.model.flat_parameters()), ptr(s0), ptr(s1), ptr(src),
+                                      src.numel(), ptr(self.scalars), stream_handle()), f"{self.kind} step")
+        else:
+            self._count_legacy()
+            check(lib().f3_rmsprop_step(ptr(self.model.flat_parameters()), ptr(self.square_avg), ptr(src),
+                                        src.numel(), self.lr, self.alpha, self.eps, scale, stream_handle()),
+                  "rmsprop")
+        if self.accum is not None:
+            self._accum_reset.fill_(1)
+
+    # -- accumulation (accum_iter > 1) ----------------------------------------------
+    def _need_accum(self, what):
+        if self.accum is None:
+            raise ValueError(f"TrainStep.{what} needs accum_iter > 1 (this step updates on every call)")
+
+    def accumulate(self):
+        """accum = grads (after an update or zero_grad()) or accum + grads: one launch, then the reset
+        word is cleared on the stream."""
+        self._need_accum("accumulate()")
+        check(lib().f3_grad_accumulate(ptr(self.accum), ptr(self.grads), self.grads.numel(),
+                                       ptr(self._accum_reset), stream_handle()), "fall3 grad accumulate")
+
+    def begin_epoch(self, num_batches):
+        """Start counting batches at 0 for the reference's update rule (accum_updates): the epoch's
+        last batch then updates too. Without it the count runs on and nothing is flushed at an epoch's end."""
+        self._i, self._num_batches = 0, int(num_batches)
+
+    def zero_grad(self):
+        """Discard a pending accumulation: the next micro-batch overwrites `accum`."""
+        self._need_accum("zero_grad()")
+        self._accum_reset.fill_(1)
+        self.pending = 0
+
+    def _update_due(self, update):
+        i = self._i
+        self._i += 1
+        if update is not None:
+            return bool(update)
+        return i % self.accum_iter == 0 or (self._num_batches is not None and i + 1 == self._num_batches)
 
     def backward_optimizer_step(self):
         """loss.backward() + optimizer.step() in one native call (world 1): each skeleton layer's
@@ -305,11 +409,28 @@ class TrainStep:
             self.backward_phase(0)
         self.optimizer_step()
 
-    def __call__(self, skel, sensor, label):
-        label = self.prepare(skel, sensor, label)
+    def _accum_call(self, skel, sensor, label, update):
+        """One micro-batch of an accumulating step; the all-reduce and the update on update calls only."""
+        do_update = self._update_due(update)
         if self.graph is None:
-            self._eager(skel, sensor, label)
-            return self.loss
+            self.forward_backward(skel, sensor, label)
+            self.accumulate()
+        else:
+            self._load_static(skel, sensor, label)
+            self.graph[0].replay()
+        self.pending += 1
+        if do_update:
+            self.sync.all()
+            if self.graph is None:
+                self.optimizer_step()
+            else:
+                if self._graph_legacy:
+                    self._legacy_steps += 1
+                self.graph[2].replay()
+            self.pending = 0
+        return self.loss
+
+    def _load_static(self, skel, sensor, label):
         s = self._static
         if skel is not None and skel.data_ptr() != s[0].data_ptr():
             s[0].copy_(skel)
@@ -317,6 +438,19 @@ class TrainStep:
             s[1].copy_(sensor)
         if label.data_ptr() != s[2].data_ptr():
             s[2].copy_(label)
+
+    def __call__(self, skel, sensor, label, update=None):
+        """One batch. `update` (accumulating steps only): True / False decides whether this call ends
+        with the optimizer update, instead of the reference's rule counted from begin_epoch()."""
+        label = self.prepare(skel, sensor, label)
+        if self.accum is not None:
+            return self._accum_call(skel, sensor, label, update)
+        if update is not None and not update:
+            self._need_accum("__call__(update=False)")
+        if self.graph is None:
+            self._eager(skel, sensor, label)
+            return self.loss
+        self._load_static(skel, sensor, label)
         g_head, g_tail, g_opt = self.graph
         if self._graph_legacy:
             self._legacy_steps += 1
@@ -335,7 +469,9 @@ class TrainStep:
         """Capture the step into HIP graphs; the given tensors become the static inputs
         (later calls copy new batches into them). world == 1: [fwd+loss+bwd], [RMSprop].
         world > 1: [fwd+loss+bwd phase 1], [bwd phase 2], [RMSprop], with the two all-reduce
-        buckets issued between replays."""
+        buckets issued between replays. accum_iter > 1: [fwd+loss+bwd+accumulate], [update on
+        accum, set the reset word]; the second is replayed on update calls only, after the all-reduce
+        of accum at world > 1. A pending accumulation is kept."""
         self._static = (skel, sensor, label)
         kept = self.metrics.snapshot() if self.metrics is not None else None  # the warm-up steps must not count
         side = torch.cuda.Stream()
@@ -356,6 +492,12 @@ class TrainStep:
             g_tail = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g_tail):
                 self.backward_phase(2)
+        elif self.accum is not None:
+            # the micro-step in its one form: the accumulate launch reads the reset word when replayed;
+            # the optimizer graph below reads accum and ends by setting the word
+            with torch.cuda.graph(g_head):
+                self.forward_backward(skel, sensor, label)
+                self.accumulate()
         else:
             with torch.cuda.graph(g_head):
                 self.forward_backward(skel, sensor, label)
@@ -369,13 +511,14 @@ class TrainStep:
     def param_grad_norms(self):
         """(names, norms): names in model.named_parameters() order; norms a device fp32 tensor of
         len(names) + 1 values, the L2 norm of each parameter's gradient and then of all of them, of the
-        gradient the last update consumed (self.grads times 1/world). Two launches, no sync (the
+        gradient the last update consumed (self.grads, or self.accum in an accumulating step, times
+        1/world; between updates `accum` holds the sum so far). Two launches, no sync (the
         reference's visualize_weights_and_gradients calls .item() per parameter, model/main.py:84-89).
         The same tensor is returned by every call: clone it to keep a step's values."""
         if self._grad_norms is None:
             views = {name: (shape, off) for name, shape, off in self.model.param_views()}
             names = [n for n, _ in self.model.named_parameters()]
-            self._grad_norms = (names, _metrics.SegmentNorms(self.grads, [views[n][1] for n in names],
+            self._grad_norms = (names, _metrics.SegmentNorms(self._gsrc, [views[n][1] for n in names],
                                                              [int(np.prod(views[n][0])) for n in names]))
         names, seg = self._grad_norms
         return list(names), seg(1.0 / self.world)
@@ -392,7 +535,9 @@ class TrainStep:
 
     def optimizer_state_dict(self):
         """torch.optim.<kind>(model.parameters()).state_dict() of this step's optimizer state: loads into
-        torch's optimizer, into f3's, and back into a TrainStep (load_optimizer_state_dict)."""
+        torch's optimizer, into f3's, and back into a TrainStep (load_optimizer_state_dict). `step` counts
+        updates, not micro-batches; a pending accumulation is not saved (the reference checkpoints at
+        epoch ends, model/main.py:336, where nothing is pending)."""
         group = self._group()
         full = _optim.torch_defaults(self.kind)
         full.update({k: v for k, v in group.items() if k != "params"})

@@ -18,6 +18,8 @@
  *   f3_metrics_update  <- cal_top_k_accuracy(), running loss, confusion matrix   model/main.py:57-77,
  *                         134-135, 189-200 (accumulated on the device: no copy or sync per batch)
  *   f3_segment_norms   <- param.grad.norm().item() per parameter   model/main.py:84-89
+ *   f3_net_loss_ex     <- CrossEntropyLoss(label_smoothing=TRAIN.LABEL_SMOOTHING)   model/main.py:280
+ *   f3_grad_accumulate <- .grad += g between the optimizer steps of TRAIN.ACCUM_ITER  model/main.py:115-132
  *
  * Conventions: plain pointers to device memory (HIP), sizes in elements, a HIP stream
  * passed as void*. No call allocates, frees or synchronises: every buffer (flat
@@ -264,6 +266,38 @@ int f3_metrics_update(void* acc, const float* out, const float* label, const int
 int64_t f3_segment_norms_scratch_bytes(int64_t total_len, int nseg);
 int f3_segment_norms(const float* g, const int64_t* seg_off, const int64_t* seg_len, int nseg, float* norms,
                      void* scratch, int64_t scratch_bytes, double scale, void* stream);
+
+/* ---- label smoothing and gradient accumulation (TRAIN.LABEL_SMOOTHING, TRAIN.ACCUM_ITER) ----
+ * f3_soft_ce_ex / f3_net_loss_ex  <- torch.nn.CrossEntropyLoss(label_smoothing=eps)(pred, label)
+ *                                    model/main.py:280 (the loss_fn of :113 train, :175 valid, :226 test)
+ * f3_grad_accumulate              <- loss.backward() adding into .grad while optimizer.step() and
+ *                                    model.zero_grad() run only every ACCUM_ITER-th batch, model/main.py:115-132
+ * torch's rule for probability targets, which it also applies to class indices as one-hot rows:
+ *   y' = y (1 - eps) + eps / C
+ *   loss = -(1/N) sum_n sum_c y'_nc log_softmax(out_n)_c
+ *   dout = (softmax(out) * sum_c y'_c - y') / N           (rows are not renormalised)
+ * Exactly one of label (f32[N,C]) and label_idx (i64[N]; an index outside [0,C) is a row of zeros, as
+ * f3_metrics_update counts it) is given. dout == NULL: the loss only (the eval loops), nothing else is
+ * written. C <= 16 keeps the row in registers, larger C reads it from memory. N <= 4096: one 256-thread
+ * workgroup stores the mean (no zeroed loss word, no atomics); at eps = 0 with a soft label this gives
+ * the bits of f3_soft_ce / f3_net_loss (the same sums in the same order). Larger N: up to 1024
+ * workgroups store one partial each into a block the library owns, and a second launch adds them in
+ * index order; such calls must not overlap on two streams. No float atomics: the same inputs give
+ * the same bits. F3_EINVAL: eps outside [0,1] or not finite, N < 1, C outside 1..64, both or neither
+ * label forms. */
+int f3_soft_ce_ex(const float* out, const float* label, const int64_t* label_idx, int N, int C,
+                  float label_smoothing, float* loss, float* dout, void* stream);
+/* f3_net_loss with smoothing: f3_soft_ce_ex(out, label, NULL, batch, num_class, ...). */
+int f3_net_loss_ex(f3_net* net, int batch, const float* out, const float* label, float label_smoothing,
+                   float* loss, float* dout, void* stream);
+/* One micro-batch's gradient into the accumulator: every thread reads the device word *reset_flag;
+ * non-zero (the first micro-batch after model.zero_grad(), main.py:132): acc[i] = grads[i], bit for
+ * bit; zero: acc[i] = acc[i] + grads[i], one fp32 add per element, the order in which autograd's
+ * in-place .grad += g sums. The word is then cleared on the same stream (a memset after the kernel),
+ * so a captured graph needs one form of the micro-step; the caller sets it again after its update.
+ * acc and grads 16-byte aligned, reset_flag 4-byte aligned, else F3_EINVAL; so is n < 0. n = 0 only
+ * clears the word. */
+int f3_grad_accumulate(float* acc, const float* grads, int64_t n, int* reset_flag, void* stream);
 
 /* Kernel-level entries used by the unit tests and bench.py: out[N,T_out,V,Cout] = conv_(KT,1)(x)
  * with x [N,T_in,V,Cin] channels-last, w in reference layout [Cout][Cin][KT], bias [Cout]
