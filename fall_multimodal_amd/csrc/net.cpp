@@ -11,7 +11,6 @@
 
 #include <algorithm>
 #include <cstdio>
-#include <functional>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -22,6 +21,7 @@
 #include "kernels.h"
 #include "layers.h"
 #include "sensor.h"
+#include "host_args.h"
 #include "fall3.h"
 
 using namespace f3;
@@ -50,10 +50,42 @@ struct BnIdx {
   int w = -1, b = -1, rm = -1, rv = -1, nbt = -1, C = 0;
 };
 
+// How a GEMM reads an activation slot. The workspace slots are untyped (float*); what a layer's slots
+// hold is fixed once, in its LayerFmt, and set on the argument blocks by set_in / set_wgrad_ops.
+enum OpFmt : int {
+  OP_F32,    // fp32 on the fp32 kernels
+  OP_F32X3,  // fp32, split into bf16 hi / lo inside the bf16x3 kernels (ConvGemmArgs / WgradArgs::x3)
+  OP_BF16,   // bf16 (bf16 mode stores its GEMM operands as bf16 in the fp32-sized slot)
+  OP_HILO,   // rows [hi | lo] of 2C bf16 on the bf16 kernels (x3n / x3seg, weights in prep code 4)
+};
+
+enum GcnRoute : int {
+  GCN_FIRST,  // the 3-channel first block on layer0.hip's fused kernels
+  GCN_FUSED,  // the mix inside the GEMM (forward: gcn_fwd.hip; backward: dgrad + mix, gcn_bwd.hip)
+  GCN_PAIR,   // two kernels through Z / dZ in HBM (forward: mix then GEMM; backward: GEMM then mix)
+};
+
+// A layer's kernel routes and operand formats: a function of (K, V, cin, cout), the precision and the
+// two F3_GCN_*_FUSED switches, decided once in f3_net_create (layer_fmt). plan(), the weight prep,
+// the forward and the backward read this record; none of them asks the predicates again.
+struct LayerFmt {
+  GcnRoute fwd, bwd;
+  bool gcat;  // bf16x3 with the split-bf16 graph mix: Z and dg as [hi | lo] rows, gcn weights in code 4
+  bool dzb;   // bf16 mode: bf16 dZ for the LDS graph-mix backward
+  OpFmt gop;  // the gcn GEMM operands Z and dg
+  OpFmt top;  // the tcn / residual operands u, dh, dres and the block-input copy xb
+  // prep codes of the packed weights (0 fp32, 1 bf16, 2 split hi / lo planes, 4 native [hi 32 | lo 32]
+  // blocks): the gcn's, and the tcn's and residual conv's
+  int gcn_code, conv_code;
+  // slot bytes per (row, channel) of the workspace tensors whose form varies; 0: the layer has none
+  int z_w, dg_w, dres_w, u_w, outb_w;
+};
+
 struct LayerIdx {
   int cin, cout, stride, res, T_in, T_out;
   int gcn_w, gcn_b, tcn_w, tcn_b, res_w = -1, res_b = -1, ca_w1, ca_b1, ca_w2, ca_b2, edge;
   BnIdx bn1, bn2, bnr, bnca;
+  LayerFmt fmt;
 };
 
 struct StreamIdx {
@@ -79,9 +111,61 @@ const int kChan[7][4] = {{-1, 64, 1, RES_NONE}, {64, 64, 1, RES_ID},    {64, 64,
                          {64, 128, 2, RES_CONV}, {128, 128, 1, RES_ID}, {128, 256, 2, RES_CONV},
                          {256, 256, 1, RES_ID}};  // stgcan.py:182-194
 
-}  // namespace
+// F3_GCN_DGRAD_FUSED=0: the gcn input-gradient GEMM and the mix backward as two kernels through an
+// fp32 dZ in HBM (the A/B baseline of gcn_bwd.hip's fused kernel); read once per process
+inline bool gcn_dgrad_fused() {
+  static const bool on = !getenv("F3_GCN_DGRAD_FUSED") || atoi(getenv("F3_GCN_DGRAD_FUSED")) != 0;
+  return on;
+}
 
-struct f3_net {
+// F3_GCN_FWD_FUSED=0: the graph mix and the gcn forward GEMM as two kernels through the Z rows in HBM
+// (the A/B baseline of gcn_fwd.hip's fused kernel); read once per process
+inline bool gcn_fwd_fused() {
+  static const bool on = !getenv("F3_GCN_FWD_FUSED") || atoi(getenv("F3_GCN_FWD_FUSED")) != 0;
+  return on;
+}
+
+// The only place that asks the shape predicates and the two switches (see LayerFmt).
+// next_res_conv: the next block has a residual conv, which reads this block's output as a GEMM operand.
+LayerFmt layer_fmt(int precision, int K, int V, int Ci, int C, int res, bool next_res_conv) {
+  const bool hb = precision == F3_PRECISION_BF16, x3 = precision == F3_PRECISION_BF16X3;
+  LayerFmt f;
+  // bf16x3: the first block's gcn (Cin = 3: a 9-column GEMM, too narrow for the bf16 implicit-GEMM
+  // kernels) runs on layer0.hip's fused kernels in their fp32 form (mix + GEMM + bias + BN1 sums in one
+  // pass; backward dZ, dx, dA and dW partials in one pass): 10.14 -> 9.92 ms/step against the generic
+  // mix + split GEMMs (profiles/r04_gcn0_x3_ab.txt)
+  const bool first = (hb || x3) && f3_gcn0_ok(K, V, Ci, C);
+  // bf16x3 with the split-bf16 graph mix (Ci = 64 / 128 / 256): the gcn GEMM operands Z and dg as rows
+  // [hi | lo] of 2 K Ci / 2C bf16 (the fp32 slot), the packed weights in the native form
+  f.gcat = x3 && f3_mix_x3_ok(K, V, Ci);
+  f.dzb = hb && f3_mix_lds_ok(K, V, Ci);
+  // layers 1-3: the mix computed into the GEMM's A blocks (gcn_fwd.hip), same bits as the pair
+  const bool fwd_fused = f.gcat && Ci == 64 && K * Ci == 192 && V <= 18 && (C == 64 || C == 128) && gcn_fwd_fused() &&
+                         f3_gcn_fwd_mix_ok(K, V, Ci, C);
+  // bf16x3: dZ, dx and dA in one pass over dg and x (gcn_bwd.hip), dZ never in HBM. Ci = 64 only:
+  // there the fused kernel makes the pair's sums in the pair's order (one channel chunk, the mix
+  // backward's frame-to-row map), so the step's results are the same bits. With Ci / 64 chunks in
+  // separate workgroups dA would be summed in another order, and RMSprop turns last-bit gradient
+  // differences into different trajectories within a few steps.
+  const bool bwd_fused = f.gcat && Ci == 64 && gcn_dgrad_fused() && f3_gcn_dgrad_mix_ok(K, V, Ci, C);
+  f.fwd = first ? GCN_FIRST : fwd_fused ? GCN_FUSED : GCN_PAIR;
+  f.bwd = first ? GCN_FIRST : bwd_fused ? GCN_FUSED : GCN_PAIR;
+  f.gop = hb ? OP_BF16 : f.gcat ? OP_HILO : x3 ? OP_F32X3 : OP_F32;
+  f.top = hb ? OP_BF16 : x3 ? OP_HILO : OP_F32;
+  // bf16x3: the bf16 implicit-GEMM kernels' packing (native [hi 32 | lo 32] blocks, code 4); the gcn
+  // weights in it only with the split-bf16 mix, fp32 for layer0.hip, else the split planes
+  const int wc = hb ? 1 : x3 ? 2 : 0;
+  f.conv_code = x3 ? x3code() : wc;
+  f.gcn_code = f.gcat ? x3code() : (x3 && first ? 0 : wc);
+  f.z_w = 4;  // fp32, bf16 in the fp32-sized slot, or [hi | lo] pairs
+  f.dg_w = 4;
+  f.dres_w = res == RES_CONV ? 4 : 0;
+  f.u_w = x3 ? 4 : hb ? 2 : 0;  // u = relu(bn1(g)): [hi | lo] rows, bf16, or not materialised (fp32 mode)
+  f.outb_w = x3 && next_res_conv ? 4 : 0;  // bf16x3: a [hi | lo] copy of the block output
+  return f;
+}
+
+struct Net {
   // branch concurrency: the position stream runs on the caller's stream, the motion stream
   // and the sensor branch on two private streams forked/joined with events (capturable)
   // aux[0]: motion stream, aux[1]: sensor branch, aux[2]: weight-gradient side stream (both
@@ -106,7 +190,7 @@ struct f3_net {
   void smark(int i, hipStream_t s) {
     if (stiming && sev[i]) (void)hipEventRecord(sev[i], s);
   }
-  ~f3_net() {
+  ~Net() {
     for (auto& e : sev) if (e) (void)hipEventDestroy(e);
     for (auto& a : aux) if (a) (void)hipStreamDestroy(a);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
@@ -190,6 +274,7 @@ struct f3_net {
       L.T_out = (T - 1) / L.stride + 1;  // (T + 2*4 - 9)/s + 1
       T = L.T_out;
       const int ci = L.cin, co = L.cout;
+      L.fmt = layer_fmt(cfg.precision, K, V, ci, co, L.res, i < 6 && kChan[i + 1][3] == RES_CONV);
       const std::string p = pre + layers + "." + std::to_string(i) + ".";
       cur_phase = i >= kSplitLayer ? 1 : 2;
       L.gcn_w = add(p + "gcn.conv.weight", F3_ENTRY_PARAM, {K * co, ci, 1, 1});
@@ -252,8 +337,6 @@ struct f3_net {
   }
 };
 
-namespace {
-
 struct Arena {
   char* base;
   size_t off = 0;
@@ -265,12 +348,6 @@ struct Arena {
     return p;
   }
 };
-
-// slab capacity: one round of resident 128x128 weight-gradient tiles (2 per CU x 256 CUs), or 16
-// splits of the 256 x 256 x 9 tcn weight (wgrad_taps: 16 tiles x 16 splits = one workgroup per
-// CU); the launchers cap the split count to it
-// capacity of a stream's weight-gradient split-K slab (floats; the bf16x3 launches use 4x this)
-constexpr long long kWgradSlabFloats = std::max(512LL * 128 * 128, 16LL * 256 * 256 * 9);
 
 struct BnWs {
   double *fsum = nullptr, *fsq = nullptr, *bsum = nullptr, *bsq = nullptr;
@@ -334,7 +411,88 @@ void bn_take_b(Arena& A, BnWs& b, int C) {
   b.bsq = A.take<double>(C);
 }
 
-Ws plan(const f3_net& net, int N, char* base) {
+// One skeleton stream's saved activations, packed weights and scratch.
+void plan_stream(const Net& net, const StreamIdx& S, StreamWs& W, int N, Arena& A) {
+  const int K = net.K, V = net.V;
+  const bool hb = net.cfg.precision == F3_PRECISION_BF16;
+  const bool x3 = net.cfg.precision == F3_PRECISION_BF16X3;
+  W.x0 = A.take<float>((size_t)N * S.T * V * S.cin);
+  W.A = A.take<float>((size_t)K * V * V);
+  size_t maxMC = 0, maxZ = 0;
+  const float* xin = W.x0;
+  const unsigned short* xinb = nullptr;
+  for (int l = 0; l < 7; ++l) {
+    const LayerIdx& L = S.L[l];
+    LayerWs& X = W.L[l];
+    const size_t Mi = (size_t)N * L.T_in * V, Mo = (size_t)N * L.T_out * V;
+    const int C = L.cout, Ci = L.cin;
+    const LayerFmt& F = L.fmt;  // what the z / u / dg / dres / outb slots hold
+    X.x = xin;
+    X.xb = xinb;
+    X.z = reinterpret_cast<float*>(A.take<char>(Mi * K * Ci * F.z_w));
+    X.g = A.take<float>(Mi * C);
+    if (F.u_w) X.u = reinterpret_cast<unsigned short*>(A.take<char>(Mi * C * F.u_w));
+    X.h = A.take<float>(Mo * C);
+    if (L.res == RES_CONV) X.r = A.take<float>(Mo * C);
+    X.out = A.take<float>(Mo * C);
+    X.q1 = A.take<float>((size_t)N * C / 4);
+    X.hid = A.take<float>((size_t)N * C / 4);
+    X.att = A.take<float>((size_t)N * C);
+    // packed GEMM weights: the fp32 slot (2 bf16 per weight) holds every form: fp32, bf16, the split
+    // hi / lo planes, and the bf16x3 native [W_hi 32 | W_lo 32] blocks (prep code 4)
+    X.gw = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * K * Ci * 2));
+    X.gwT = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * K * Ci * 2));
+    X.tw = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * 9 * C * 2));
+    X.twT = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * 9 * C * 2));
+    if (L.res == RES_CONV) {
+      X.rw = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * Ci * 2));
+      X.rwT = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * Ci * 2));
+    }
+    X.aeff = A.take<float>((size_t)K * V * V);
+    X.beff = A.take<float>((size_t)V * C);
+    X.dq2 = A.take<float>((size_t)N * C);
+    X.dbn = A.take<float>((size_t)N * C / 4);
+    X.dq1 = A.take<float>((size_t)N * C / 4);
+    X.e = A.take<float>((size_t)N * C);
+    X.dh = reinterpret_cast<float*>(A.take<unsigned short>(Mo * C * 2));  // x3: [hi | lo] rows
+    X.dg = reinterpret_cast<float*>(A.take<char>(Mi * C * F.dg_w));
+    X.gpart = A.take<float>((size_t)f3_bn_bwd_parts(N, L.T_in * V, V) * V * C);
+    if (x3) X.dbpart = A.take<float>((size_t)f3_block_chunks(L.T_out * V) * N * 2 * C);
+    X.mixpart = A.take<float>((size_t)kMixParts * K * V * V);
+    if (F.dres_w) X.dres = reinterpret_cast<float*>(A.take<char>(Mo * C * F.dres_w));
+    xin = X.out;
+    // bf16 mode: the block output itself is stored bf16 (the next block's residual-conv operand);
+    // bf16x3: a [hi | lo] copy of it when the next block has a residual conv
+    xinb = hb ? reinterpret_cast<const unsigned short*>(X.out) : nullptr;
+    if (F.outb_w) xinb = X.outb = reinterpret_cast<unsigned short*>(A.take<char>(Mo * C * F.outb_w));
+    maxMC = std::max(maxMC, std::max(Mi * C, Mi * Ci));
+    maxMC = std::max(maxMC, Mo * C);
+    maxZ = std::max(maxZ, Mi * K * Ci);
+  }
+
+  W.dv = A.take<float>(maxMC);
+  W.slab = A.take<float>(kWgradSlabFloats * (x3 ? 4 : 1));  // x3: [2C][9][2C] partials
+
+  W.dZ = A.take<float>(maxZ);
+  W.dx[0] = A.take<float>(maxMC);
+  W.dx[1] = A.take<float>(maxMC);
+  W.dpool = A.take<float>((size_t)N * 256);
+  {  // partial-row regions (see StreamWs::detm / dets)
+    size_t m = (size_t)((S.T * V + 95) / 96) * N * 256;  // pool partials of the last block
+    size_t d = 0;
+    for (int l = 0; l < 7; ++l) {
+      const LayerIdx& L = S.L[l];
+      const size_t ch = (size_t)(L.T_out * V + 95) / 96;  // f3_block_* chunks per clip
+      m = std::max(m, 3 * ch * N * L.cout);
+      d = std::max(d, (size_t)((N + 7) / 8) * (2 * (L.cout / 4) * L.cout + L.cout));
+    }
+    m = std::max(m, (size_t)((N * S.T + 31) / 32) * 2 * V * S.cin);  // data_bn gamma / beta partials
+    W.detm = A.take<float>(m);
+    W.dets = A.take<float>(d);
+  }
+}
+
+Ws plan(const Net& net, int N, char* base) {
   Ws w;
   std::memset(&w, 0, sizeof(w));
   Arena A{base};
@@ -342,8 +500,6 @@ Ws plan(const f3_net& net, int N, char* base) {
   const bool cnn = net.has_cnn;
   const int Ts = net.cfg.sensor_frames;
   const int Tl = cnn ? (Ts / 2) / 2 : Ts;
-  const bool hb = net.cfg.precision == F3_PRECISION_BF16;
-  const bool x3 = net.cfg.precision == F3_PRECISION_BF16X3;
   // ---- zero-at-forward region ----
   w.zf0 = A.take<char>(0);
   w.zero = reinterpret_cast<const unsigned short*>(A.take<char>(256));
@@ -398,88 +554,7 @@ Ws plan(const f3_net& net, int N, char* base) {
   }
   w.zb1 = A.take<char>(0);
   // ---- saved activations, packed weights, scratch ----
-  for (int si = 0; si < net.nstreams; ++si) {
-    const StreamIdx& S = net.st[si];
-    StreamWs& W = w.st[si];
-    W.x0 = A.take<float>((size_t)N * S.T * V * S.cin);
-    W.A = A.take<float>((size_t)K * V * V);
-    size_t maxMC = 0, maxZ = 0;
-    const float* xin = W.x0;
-    const unsigned short* xinb = nullptr;
-    for (int l = 0; l < 7; ++l) {
-      const LayerIdx& L = S.L[l];
-      LayerWs& X = W.L[l];
-      const size_t Mi = (size_t)N * L.T_in * V, Mo = (size_t)N * L.T_out * V;
-      const int C = L.cout, Ci = L.cin;
-      // bf16x3 with the split-bf16 graph mix (Ci = 64 / 128 / 256): the gcn GEMM operands Z and dg
-      // as rows [hi | lo] of 2 K Ci / 2C bf16 (the fp32 slot), the packed weights in the native form
-      const bool gcat = x3 && f3_mix_x3_ok(K, V, Ci);
-      X.x = xin;
-      X.xb = xinb;
-      X.z = gcat ? reinterpret_cast<float*>(A.take<unsigned short>(2 * Mi * K * Ci)) : A.take<float>(Mi * K * Ci);
-      X.g = A.take<float>(Mi * C);
-      // u = relu(bn1(g)): bf16 (bf16 mode) or rows [hi | lo] of 2C bf16 (bf16x3 mode)
-      if (hb || x3) X.u = A.take<unsigned short>((x3 ? 2 : 1) * Mi * C);
-      X.h = A.take<float>(Mo * C);
-      if (L.res == RES_CONV) X.r = A.take<float>(Mo * C);
-      X.out = A.take<float>(Mo * C);
-      X.q1 = A.take<float>((size_t)N * C / 4);
-      X.hid = A.take<float>((size_t)N * C / 4);
-      X.att = A.take<float>((size_t)N * C);
-      // packed GEMM weights: the fp32 slot (2 bf16 per weight) holds every form: fp32, bf16, the split
-      // hi / lo planes, and the bf16x3 native [W_hi 32 | W_lo 32] blocks (prep code 4)
-      X.gw = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * K * Ci * 2));
-      X.gwT = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * K * Ci * 2));
-      X.tw = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * 9 * C * 2));
-      X.twT = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * 9 * C * 2));
-      if (L.res == RES_CONV) {
-        X.rw = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * Ci * 2));
-        X.rwT = reinterpret_cast<float*>(A.take<unsigned short>((size_t)C * Ci * 2));
-      }
-      X.aeff = A.take<float>((size_t)K * V * V);
-      X.beff = A.take<float>((size_t)V * C);
-      X.dq2 = A.take<float>((size_t)N * C);
-      X.dbn = A.take<float>((size_t)N * C / 4);
-      X.dq1 = A.take<float>((size_t)N * C / 4);
-      X.e = A.take<float>((size_t)N * C);
-      X.dh = reinterpret_cast<float*>(A.take<unsigned short>(Mo * C * 2));  // x3: [hi | lo] rows
-      X.dg = gcat ? reinterpret_cast<float*>(A.take<unsigned short>(2 * Mi * C)) : A.take<float>(Mi * C);
-      X.gpart = A.take<float>((size_t)f3_bn_bwd_parts(N, L.T_in * V, V) * V * C);
-      if (x3) X.dbpart = A.take<float>((size_t)f3_block_chunks(L.T_out * V) * N * 2 * C);
-      X.mixpart = A.take<float>((size_t)kMixParts * K * V * V);
-      // (bf16x3: dres as rows [hi | lo] of 2C bf16)
-      if (L.res == RES_CONV) X.dres = x3 ? reinterpret_cast<float*>(A.take<unsigned short>(2 * Mo * C)) : A.take<float>(Mo * C);
-      xin = X.out;
-      // bf16 mode: the block output itself is stored bf16 (the next block's residual-conv operand);
-      // bf16x3: a [hi | lo] copy of it when the next block has a residual conv
-      xinb = hb ? reinterpret_cast<const unsigned short*>(X.out) : nullptr;
-      if (x3 && l < 6 && S.L[l + 1].res == RES_CONV) xinb = X.outb = A.take<unsigned short>(2 * Mo * C);
-      maxMC = std::max(maxMC, std::max(Mi * C, Mi * Ci));
-      maxMC = std::max(maxMC, Mo * C);
-      maxZ = std::max(maxZ, Mi * K * Ci);
-    }
-
-    W.dv = A.take<float>(maxMC);
-    W.slab = A.take<float>(kWgradSlabFloats * (x3 ? 4 : 1));  // x3: [2C][9][2C] partials
-
-    W.dZ = A.take<float>(maxZ);
-    W.dx[0] = A.take<float>(maxMC);
-    W.dx[1] = A.take<float>(maxMC);
-    W.dpool = A.take<float>((size_t)N * 256);
-    {  // partial-row regions (see StreamWs::detm / dets)
-      size_t m = (size_t)((S.T * V + 95) / 96) * N * 256;  // pool partials of the last block
-      size_t d = 0;
-      for (int l = 0; l < 7; ++l) {
-        const LayerIdx& L = S.L[l];
-        const size_t ch = (size_t)(L.T_out * V + 95) / 96;  // f3_block_* chunks per clip
-        m = std::max(m, 3 * ch * N * L.cout);
-        d = std::max(d, (size_t)((N + 7) / 8) * (2 * (L.cout / 4) * L.cout + L.cout));
-      }
-      m = std::max(m, (size_t)((N * S.T + 31) / 32) * 2 * V * S.cin);  // data_bn gamma / beta partials
-      W.detm = A.take<float>(m);
-      W.dets = A.take<float>(d);
-    }
-  }
+  for (int si = 0; si < net.nstreams; ++si) plan_stream(net, net.st[si], w.st[si], N, A);
   if (net.has_sensor) {
     if (cnn) {
       w.y1 = A.take<float>((size_t)N * Ts * 16);
@@ -515,7 +590,7 @@ Ws plan(const f3_net& net, int N, char* base) {
 }
 
 struct Ptrs {
-  const f3_net& net;
+  const Net& net;
   const float* P;
   float* B;
   int64_t* C;
@@ -545,26 +620,8 @@ struct Ptrs {
 };
 
 
-ConvGeom geom(int M, int Nc, int Kc, int KT, int S, int P, int tr, int T_out, int T_in, int V, int lda, int ldo) {
-  ConvGeom g;
-  g.M = M; g.Nc = Nc; g.Kc = Kc; g.KT = KT; g.S = S; g.P = P; g.transposed = tr;
-  g.T_out = T_out; g.T_in = T_in; g.V = V; g.lda = lda; g.ldo = ldo;
-  return g;
-}
-
-void add_job(PrepTable& t, int type, int n, float* dst, const float* s0, const float* s1, const float* s2, int d0,
-             int d1, int d2, int bf16 = 0) {
-  PrepJob& j = t.jobs[t.n++];
-  j.type = type; j.n = n; j.dst = dst; j.s0 = s0; j.s1 = s1; j.s2 = s2; j.d0 = d0; j.d1 = d1; j.d2 = d2;
-  j.bf16 = bf16;
-}
-
-// bf16 view of a packed operand (the fp32-sized slot holds the bf16 copy in bf16 mode)
-inline const unsigned short* bf(const float* p, int on) { return on ? reinterpret_cast<const unsigned short*>(p) : nullptr; }
-// bf16x3 mode (F3_PRECISION_BF16X3, the default): fp32 activations as in the fp32 mode; GEMM operands
-// as bf16 rows [x_hi | x_lo] written by their producers and weights packed per tap in 32-channel
-// blocks [W_hi | W_lo] (prep code 4), three bf16 MFMA products per block (x3_gemm below)
-inline int is_x3(const f3_net& n) { return n.cfg.precision == F3_PRECISION_BF16X3; }
+inline int is_x3(const Net& n) { return n.cfg.precision == F3_PRECISION_BF16X3; }
+inline int is_bf16(const Net& n) { return n.cfg.precision == F3_PRECISION_BF16; }
 // Side-queue weight gradients of layers >= 2 are split for 75 % of the chip's workgroup slots, so the
 // main chains running beside them keep CUs (a whole-chip wgrad_big grid holds every CU's LDS until it
 // drains: the main queues sat idle 190-335 us behind the layer-5 weight gradient,
@@ -572,41 +629,44 @@ inline int is_x3(const f3_net& n) { return n.cfg.precision == F3_PRECISION_BF16X
 // chip. Measured (bf16x3 step): 10.17 -> 10.07 ms at 50 or 75 %, flat over 50-90 % and the first split
 // layer 0-2 (profiles/r04_ntw_ab.txt, r04_frac_ab.txt)
 inline int side_pct(bool split, int l) { return split && l >= 2 ? 75 : 0; }
-// bf16x3: the first block's gcn (Cin = 3: a 9-column GEMM, too narrow for the bf16 implicit-GEMM kernels)
-// runs on layer0.hip's fused kernels in their fp32 form (mix + GEMM + bias + BN1 sums in one pass;
-// backward dZ, dx, dA and dW partials in one pass): 10.14 -> 9.92 ms/step against the generic mix +
-// split GEMMs (profiles/r04_gcn0_x3_ab.txt)
-// bf16x3 GEMMs on the bf16 kernels in the native form (ConvGemmArgs::x3n, prep code 4: [x_hi | x_lo]
-// rows staged once, three MFMAs per 32-channel block). The round-4 K-concatenated form (Kc = 3C,
-// [W_hi | W_hi | W_lo], the third K segment re-staging x_hi) measured 8 % slower per step (9.97-10.02
-// vs 9.11-9.12 ms, profiles/r05_x3n_ab.txt) and is gone.
-constexpr int x3code() { return 4; }
-// packed size (bf16 elements) of n weights in a prep code
-inline int x3mul(int code) { return code == 4 ? 2 : 1; }
-// set a bf16x3 GEMM on [hi | lo] rows of C channels (lda 2C)
-inline void x3_gemm(ConvGemmArgs& a, int C) {
-  a.x3n = 1;
-  a.g.lda = 2 * C;
+
+// The input operand of a GEMM: rows of C channels in `slot`, held in format f. Call after a.g is set
+// (the [hi | lo] rows double lda).
+inline void set_in(ConvGemmArgs& a, const void* slot, int C, OpFmt f) {
+  const bool b16 = f == OP_BF16 || f == OP_HILO;
+  a.in = b16 ? nullptr : static_cast<const float*>(slot);
+  a.inb = b16 ? static_cast<const unsigned short*>(slot) : nullptr;
+  a.x3 = f == OP_F32X3;
+  if (f == OP_HILO) x3_gemm(a, C);
 }
 
-// F3_GCN_DGRAD_FUSED=0: the gcn input-gradient GEMM and the mix backward as two kernels through an
-// fp32 dZ in HBM (the A/B baseline of gcn_bwd.hip's fused kernel); read once per process
-inline bool gcn_dgrad_fused() {
-  static const bool on = !getenv("F3_GCN_DGRAD_FUSED") || atoi(getenv("F3_GCN_DGRAD_FUSED")) != 0;
-  return on;
+// The operand pair of a weight gradient: output-gradient rows of Cy channels and forward-input rows of
+// Cx channels, both in format f. Call after a.g and a.ldy are set. The [hi | lo] rows run on the bf16
+// kernels as three row segments (dy_hi x_hi, dy_lo x_hi, dy_hi x_lo). (One GEMM on [dy_hi | dy_lo] x
+// [x_hi | x_lo] whose quadrants a fold adds computes the unused lo*lo quadrant too: 11.31 vs 10.78
+// ms/step.) slab != null: the bf16 kernels' split partials go to the stream's slab (4x the floats for
+// the segments) and are summed into dw.
+inline void set_wgrad_ops(WgradArgs& a, const void* dy, int Cy, const void* in, int Cx, OpFmt f,
+                          const unsigned short* zero, float* slab, float* dw) {
+  const bool b16 = f == OP_BF16 || f == OP_HILO;
+  a.dy = b16 ? nullptr : static_cast<const float*>(dy);
+  a.in = b16 ? nullptr : static_cast<const float*>(in);
+  a.dyb = b16 ? static_cast<const unsigned short*>(dy) : nullptr;
+  a.inb = b16 ? static_cast<const unsigned short*>(in) : nullptr;
+  a.bf16 = b16;
+  a.x3 = f == OP_F32X3;
+  if (b16) a.zero = zero;
+  if (b16 && slab) {
+    a.slab = slab;
+    a.slab_cap = kWgradSlabFloats * (f == OP_HILO ? 4 : 1);
+    a.dw_ref = dw;
+  }
+  if (f == OP_HILO) {
+    a.ldy = 2 * Cy;
+    a.g.lda = 2 * Cx;
+    a.x3seg = 1;
+  }
 }
-
-// F3_GCN_FWD_FUSED=0: the graph mix and the gcn forward GEMM as two kernels through the Z rows in HBM
-// (the A/B baseline of gcn_fwd.hip's fused kernel); read once per process
-inline bool gcn_fwd_fused() {
-  static const bool on = !getenv("F3_GCN_FWD_FUSED") || atoi(getenv("F3_GCN_FWD_FUSED")) != 0;
-  return on;
-}
-
-// prep code of the packed GEMM weights: 0 fp32, 1 bf16, 2 split hi / lo planes
-inline int wcode(const f3_net& n) { return n.cfg.precision == F3_PRECISION_BF16 ? 1 : is_x3(n) ? 2 : 0; }
-// bf16 view of an activation slot (bf16 mode stores GEMM operand tensors as bf16)
-inline unsigned short* bfa(float* p, int on) { return on ? reinterpret_cast<unsigned short*>(p) : nullptr; }
 
 void add_bnrun(BnRunTable& t, const Ptrs& q, const BnIdx& bi, const double* sum, const double* sq, double count) {
   BnRunJob& j = t.jobs[t.n++];
@@ -614,21 +674,16 @@ void add_bnrun(BnRunTable& t, const Ptrs& q, const BnIdx& bi, const double* sum,
   j.rmean = q.b(bi.rm); j.rvar = q.b(bi.rv); j.nbt = q.c(bi.nbt);
 }
 
-// Forward of one skeleton stream in stages: stage -1 = weight prep + data_bn, stage l = block l.
-// The caller interleaves the two streams' stages so both branch queues are fed from the start
-// (host submission, eager or graph replay, walks the launches in issue order).
-int stream_forward_layer(const f3_net& net, int si, int N, int train, const Ptrs& q, Ws& w, BnRunTable& run,
-                         hipStream_t s, int l);
+// The forward of one skeleton stream is stream_prep, then layer_forward for blocks 0..6. The caller
+// interleaves the two streams' calls so both branch queues are fed from the start (host submission,
+// eager or graph replay, walks the launches in issue order).
 
-int stream_forward(const f3_net& net, int si, int N, int train, const Ptrs& q, Ws& w, const float* skel,
-                   BnRunTable& run, hipStream_t s, int stage) {
-  if (stage >= 0) return stream_forward_layer(net, si, N, train, q, w, run, s, stage);
+// Weight prep (A_eff, the gcn bias through the graph, the packed GEMM operands) and data_bn.
+int stream_prep(const Net& net, int si, int N, int train, const Ptrs& q, Ws& w, const float* skel, BnRunTable& run,
+                hipStream_t s) {
   const StreamIdx& S = net.st[si];
   StreamWs& W = w.st[si];
   const int K = net.K, V = net.V, eval = !train;
-  const int hb = net.cfg.precision == F3_PRECISION_BF16;
-  const int wc = wcode(net);
-  // weights: A_eff, gcn bias through the graph, packed GEMM operands
   PrepTable pt;
   pt.n = 0;
   add_job(pt, PREP_COPY, K * V * V, W.A, q.b(S.A), nullptr, nullptr, 0, 0, 0);
@@ -636,13 +691,9 @@ int stream_forward(const f3_net& net, int si, int N, int train, const Ptrs& q, W
     const LayerIdx& L = S.L[l];
     LayerWs& X = W.L[l];
     const int C = L.cout, Ci = L.cin;
+    const int gc = L.fmt.gcn_code, xc = L.fmt.conv_code;
     add_job(pt, PREP_MUL, K * V * V, X.aeff, q.b(S.A), q.p(L.edge), nullptr, 0, 0, 0);
     add_job(pt, PREP_GCN_BIAS, V * C, X.beff, q.b(S.A), q.p(L.edge), q.p(L.gcn_b), C, V, K);
-    // bf16x3 with the split-bf16 mix: native-form gcn weights (code 4) for the bf16 kernels
-    const bool l0f = wc == 2 && f3_gcn0_ok(K, V, Ci, C);  // fp32 weights (layer0.hip)
-    // bf16x3: the bf16 implicit-GEMM kernels' packing (native [hi 32 | lo 32] blocks, code 4)
-    const int xc = wc == 2 ? x3code() : wc;
-    const int gc = wc == 2 && f3_mix_x3_ok(K, V, Ci) ? xc : (l0f ? 0 : wc);
     add_job(pt, PREP_PACK_GCN, C * K * Ci * x3mul(gc), X.gw, q.p(L.gcn_w), nullptr, nullptr, C, Ci, K, gc);
     add_job(pt, PREP_PACK_CONV, C * 9 * C * x3mul(xc), X.tw, q.p(L.tcn_w), nullptr, nullptr, C, C, 9, xc);
     if (train) {
@@ -655,132 +706,121 @@ int stream_forward(const f3_net& net, int si, int N, int train, const Ptrs& q, W
     }
   }
   F3_TRY(f3_prep(pt, s));
-  // data_bn
   DataBnArgs d;
   std::memset(&d, 0, sizeof(d));
   d.N = N; d.T = S.T; d.V = V; d.C = S.cin; d.motion = S.motion; d.skel = skel; d.out = W.x0;
   d.bn = q.ref(S.dbn, W.dbn, (float)(N * S.T), eval);
   d.st_sum = W.dbn.fsum; d.st_sq = W.dbn.fsq;
-  d.act16 = hb;  // bf16 mode: activations stored bf16
+  d.act16 = is_bf16(net);  // bf16 mode: activations stored bf16
   F3_TRY(f3_databn_fwd(&d, s));
   if (train) add_bnrun(run, q, S.dbn, W.dbn.fsum, W.dbn.fsq, (double)N * S.T);
   return F3_OK;
 }
 
-int stream_forward_layer(const f3_net& net, int si, int N, int train, const Ptrs& q, Ws& w, BnRunTable& run,
-                         hipStream_t s, int l) {
+// Block l of skeleton stream si.
+int layer_forward(const Net& net, int si, int l, int N, int train, const Ptrs& q, Ws& w, BnRunTable& run,
+                  hipStream_t s) {
   const StreamIdx& S = net.st[si];
   StreamWs& W = w.st[si];
+  const LayerIdx& L = S.L[l];
+  const LayerFmt& F = L.fmt;
+  LayerWs& X = W.L[l];
   const int K = net.K, V = net.V, eval = !train;
-  const int hb = net.cfg.precision == F3_PRECISION_BF16;
-  const int x3 = is_x3(net), wq = hb || x3;
-  {
-    const LayerIdx& L = S.L[l];
-    LayerWs& X = W.L[l];
-    const int C = L.cout, Ci = L.cin, Ti = L.T_in, To = L.T_out;
-    const int Mi = N * Ti * V, Mo = N * To * V;
-    const BnRef bn1 = q.ref(L.bn1, X.bn1, (float)Mi, eval);
-    const BnRef bn2 = q.ref(L.bn2, X.bn2, (float)Mo, eval);
-    BnRef bnr;
-    std::memset(&bnr, 0, sizeof(bnr));
-    if (L.res == RES_CONV) bnr = q.ref(L.bnr, X.bnr, (float)Mo, eval);
-    // graph mix then 1x1 conv (stgcan.py:50-56)
-    if ((hb || x3) && f3_gcn0_ok(K, V, Ci, C)) {  // the 3-channel first block: one kernel (layer0.hip)
-      Gcn0Args g0;
-      std::memset(&g0, 0, sizeof(g0));
-      g0.frames = N * Ti; g0.K = K; g0.V = V; g0.Ci = Ci; g0.A = X.aeff;
-      g0.x = reinterpret_cast<const unsigned short*>(X.x); g0.w = bf(X.gw, 1); g0.beff = X.beff;
-      g0.z = bfa(X.z, 1); g0.g = bfa(X.g, 1); g0.st_sum = X.bn1.fsum; g0.st_sq = X.bn1.fsq;
-      g0.f32 = x3;  // bf16x3: fp32 x / w / Z / g behind the same pointers
-      F3_TRY(f3_gcn0_fwd(&g0, s));
-    } else if (x3 && f3_mix_x3_ok(K, V, Ci) && Ci == 64 && K * Ci == 192 && V <= 18 && (C == 64 || C == 128) &&
-               gcn_fwd_fused() && f3_gcn_fwd_mix_ok(K, V, Ci, C)) {
-      // layers 1-3: the mix computed into the GEMM's A blocks (gcn_fwd.hip), same bits as the pair below
-      GcnFwdMixArgs gf;
-      std::memset(&gf, 0, sizeof(gf));
-      gf.frames = N * Ti; gf.K = K; gf.V = V; gf.Cin = Ci; gf.C = C; gf.A = X.aeff; gf.x = X.x;
-      gf.z3 = bfa(X.z, 1); gf.w = bf(X.gw, 1); gf.bias = X.beff; gf.g = X.g;
-      gf.st_sum = X.bn1.fsum; gf.st_sq = X.bn1.fsq; gf.zero = w.zero;
-      F3_TRY(f3_gcn_fwd_mix(&gf, s));
-    } else {
-      MixArgs mx;
-      std::memset(&mx, 0, sizeof(mx));
-      mx.K = K; mx.V = V; mx.Cin = Ci; mx.frames = N * Ti; mx.A = X.aeff; mx.x = X.x; mx.z = X.z;
-      mx.zb = bfa(X.z, hb); mx.x16 = hb; mx.x3 = x3;
-      const bool gcat = x3 && f3_mix_x3_ok(K, V, Ci);
-      mx.z3 = bfa(X.z, gcat);
-      F3_TRY(f3_mix_fwd(&mx, s));
-      ConvGemmArgs ga;
-      std::memset(&ga, 0, sizeof(ga));
-      ga.g = geom(Mi, C, K * Ci, 1, 1, 0, 0, Ti, Ti, V, K * Ci, C);
-      ga.in = hb ? nullptr : X.z; ga.inb = bfa(X.z, hb); ga.zero = w.zero;
-      ga.w = X.gw; ga.wb = bf(X.gw, wq); ga.out = X.g; ga.outb = bfa(X.g, hb); ga.x3 = x3;
-      ga.bias = X.beff; ga.st_sum = X.bn1.fsum; ga.st_sq = X.bn1.fsq;
-      if (gcat) {  // the [Z_hi | Z_lo] rows of K Ci channels on the bf16 kernels
-        ga.x3 = 0; ga.in = nullptr; ga.inb = bfa(X.z, 1);
-        x3_gemm(ga, K * Ci);
-      }
-      F3_TRY(f3_conv_gemm(&ga, 0, EPI_BIASV | EPI_STATS, s));
-    }
-    if (L.res == RES_CONV) {  // residual conv (stgcan.py:128-131)
-      ConvGemmArgs ra;
-      std::memset(&ra, 0, sizeof(ra));
-      ra.g = geom(Mo, C, Ci, 1, L.stride, 0, 0, To, Ti, V, Ci, C);
-      ra.in = hb ? nullptr : X.x; ra.inb = hb ? X.xb : nullptr; ra.zero = w.zero;
-      if (hb && !X.xb) return F3_ESTATE;
-      ra.w = X.rw; ra.wb = bf(X.rw, wq); ra.out = X.r; ra.outb = bfa(X.r, hb); ra.x3 = x3;
-      ra.bias = q.p(L.res_b); ra.st_sum = X.bnr.fsum; ra.st_sq = X.bnr.fsq;
-      if (x3) {  // the previous block's [x_hi | x_lo] copy
-        if (!X.xb) return F3_ESTATE;
-        ra.x3 = 0; ra.in = nullptr; ra.inb = X.xb;
-        x3_gemm(ra, Ci);
-      }
-      F3_TRY(f3_conv_gemm(&ra, 0, EPI_BIAS | EPI_STATS, s));
-    }
-    // tcn: BN1 + ReLU prologue, (9,1) conv, bias, BN2 stats + channel-attention pool epilogue
-    ConvGemmArgs ta;
-    std::memset(&ta, 0, sizeof(ta));
-    ta.g = geom(Mo, C, C, 9, L.stride, 4, 0, To, Ti, V, C, C);
-    ta.w = X.tw; ta.wb = bf(X.tw, wq); ta.out = X.h; ta.outb = bfa(X.h, hb); ta.bias = q.p(L.tcn_b);
-    ta.st_sum = X.bn2.fsum; ta.st_sq = X.bn2.fsq; ta.gap = X.gap;
-    if (hb || x3) {  // materialise u = relu(bn1(g)) once (also the tcn wgrad operand): bf16, or
-      // (bf16x3) rows [u_hi | u_lo | u_hi] against the packed [W_hi | W_hi | W_lo]: the bf16 LDS-DMA
-      // implicit-GEMM kernels then compute u_hi W_hi + u_lo W_hi + u_hi W_lo over K = 9 x 3C
-      BnReluArgs br;
-      std::memset(&br, 0, sizeof(br));
-      br.M = Mi; br.C = C; br.bn = bn1; br.g = X.g; br.u = X.u; br.g16 = hb; br.x3 = x3;
-      F3_TRY(f3_bnrelu_bf16(&br, s));
-      if (x3) x3_gemm(ta, C);
-      ta.inb = X.u; ta.zero = w.zero;
-      F3_TRY(f3_conv_gemm(&ta, 0, EPI_BIAS | EPI_STATS | EPI_GAP, s));
-    } else {
-      ta.in = X.g; ta.pro_bn = bn1;
-      F3_TRY(f3_conv_gemm(&ta, 1, EPI_BIAS | EPI_STATS | EPI_GAP, s));
-    }
-    // channel attention (stgcan.py:59-74)
-    CaArgs ca;
-    std::memset(&ca, 0, sizeof(ca));
-    ca.N = N; ca.C = C; ca.inv_tv = 1.f / (float)(To * V); ca.bn2 = bn2;
-    ca.bnca = q.ref(L.bnca, X.bnca, (float)N, eval);
-    ca.W1 = q.p(L.ca_w1); ca.b1 = q.p(L.ca_b1); ca.W2 = q.p(L.ca_w2); ca.b2 = q.p(L.ca_b2);
-    ca.gapsum = X.gap; ca.q1 = X.q1; ca.hid = X.hid; ca.att = X.att; ca.ca_sum = X.bnca.fsum; ca.ca_sq = X.bnca.fsq;
-    F3_TRY(f3_ca_fwd(&ca, s));
-    // residual add + ReLU (stgcan.py:143-144), pooled mean after the last block (stgcan.py:224)
-    BlockArgs ba;
-    std::memset(&ba, 0, sizeof(ba));
-    ba.N = N; ba.TV = To * V; ba.C = C; ba.res_kind = L.res; ba.inv_tv = 1.f / (float)(To * V);
-    ba.bn2 = bn2; ba.bnr = bnr; ba.h = X.h; ba.r = X.r; ba.x = X.x; ba.att = X.att; ba.out = X.out;
-    ba.pool = l == 6 ? W.pool : nullptr;
-    ba.part = W.detm;
-    ba.act16 = hb;
-    if (x3 && X.outb) { ba.outb = X.outb; ba.x3 = 1; }
-    F3_TRY(f3_block_out(ba, s));
-    if (train) {
-      add_bnrun(run, q, L.bn1, X.bn1.fsum, X.bn1.fsq, Mi);
-      add_bnrun(run, q, L.bn2, X.bn2.fsum, X.bn2.fsq, Mo);
-      if (L.res == RES_CONV) add_bnrun(run, q, L.bnr, X.bnr.fsum, X.bnr.fsq, Mo);
-      add_bnrun(run, q, L.bnca, X.bnca.fsum, X.bnca.fsq, N);
-    }
+  const int hb = is_bf16(net), x3 = is_x3(net), wq = hb || x3;
+  const int C = L.cout, Ci = L.cin, Ti = L.T_in, To = L.T_out;
+  const int Mi = N * Ti * V, Mo = N * To * V;
+  const BnRef bn1 = q.ref(L.bn1, X.bn1, (float)Mi, eval);
+  const BnRef bn2 = q.ref(L.bn2, X.bn2, (float)Mo, eval);
+  BnRef bnr;
+  std::memset(&bnr, 0, sizeof(bnr));
+  if (L.res == RES_CONV) bnr = q.ref(L.bnr, X.bnr, (float)Mo, eval);
+  // graph mix then 1x1 conv (stgcan.py:50-56)
+  if (F.fwd == GCN_FIRST) {
+    Gcn0Args g0;
+    std::memset(&g0, 0, sizeof(g0));
+    g0.frames = N * Ti; g0.K = K; g0.V = V; g0.Ci = Ci; g0.A = X.aeff;
+    g0.x = reinterpret_cast<const unsigned short*>(X.x); g0.w = bf(X.gw, 1); g0.beff = X.beff;
+    g0.z = bfa(X.z, 1); g0.g = bfa(X.g, 1); g0.st_sum = X.bn1.fsum; g0.st_sq = X.bn1.fsq;
+    g0.f32 = x3;  // bf16x3: fp32 x / w / Z / g behind the same pointers
+    F3_TRY(f3_gcn0_fwd(&g0, s));
+  } else if (F.fwd == GCN_FUSED) {
+    GcnFwdMixArgs gf;
+    std::memset(&gf, 0, sizeof(gf));
+    gf.frames = N * Ti; gf.K = K; gf.V = V; gf.Cin = Ci; gf.C = C; gf.A = X.aeff; gf.x = X.x;
+    gf.z3 = bfa(X.z, 1); gf.w = bf(X.gw, 1); gf.bias = X.beff; gf.g = X.g;
+    gf.st_sum = X.bn1.fsum; gf.st_sq = X.bn1.fsq; gf.zero = w.zero;
+    F3_TRY(f3_gcn_fwd_mix(&gf, s));
+  } else {
+    MixArgs mx;
+    std::memset(&mx, 0, sizeof(mx));
+    mx.K = K; mx.V = V; mx.Cin = Ci; mx.frames = N * Ti; mx.A = X.aeff; mx.x = X.x; mx.z = X.z;
+    mx.zb = bfa(X.z, hb); mx.x16 = hb; mx.x3 = x3;
+    mx.z3 = bfa(X.z, F.gcat);
+    F3_TRY(f3_mix_fwd(&mx, s));
+    ConvGemmArgs ga;
+    std::memset(&ga, 0, sizeof(ga));
+    ga.g = geom(Mi, C, K * Ci, 1, 1, 0, 0, Ti, Ti, V, K * Ci, C);
+    set_in(ga, X.z, K * Ci, F.gop);
+    ga.zero = w.zero;
+    ga.w = X.gw; ga.wb = bf(X.gw, wq); ga.out = X.g; ga.outb = bfa(X.g, hb);
+    ga.bias = X.beff; ga.st_sum = X.bn1.fsum; ga.st_sq = X.bn1.fsq;
+    F3_TRY(f3_conv_gemm(&ga, 0, EPI_BIASV | EPI_STATS, s));
+  }
+  if (L.res == RES_CONV) {  // residual conv (stgcan.py:128-131)
+    ConvGemmArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    ra.g = geom(Mo, C, Ci, 1, L.stride, 0, 0, To, Ti, V, Ci, C);
+    // bf16: the previous block's bf16 output; bf16x3: its [x_hi | x_lo] copy
+    if (F.top != OP_F32 && !X.xb) return F3_ESTATE;
+    set_in(ra, F.top == OP_F32 ? static_cast<const void*>(X.x) : X.xb, Ci, F.top);
+    ra.zero = w.zero;
+    ra.w = X.rw; ra.wb = bf(X.rw, wq); ra.out = X.r; ra.outb = bfa(X.r, hb);
+    ra.bias = q.p(L.res_b); ra.st_sum = X.bnr.fsum; ra.st_sq = X.bnr.fsq;
+    F3_TRY(f3_conv_gemm(&ra, 0, EPI_BIAS | EPI_STATS, s));
+  }
+  // tcn: BN1 + ReLU prologue, (9,1) conv, bias, BN2 stats + channel-attention pool epilogue
+  ConvGemmArgs ta;
+  std::memset(&ta, 0, sizeof(ta));
+  ta.g = geom(Mo, C, C, 9, L.stride, 4, 0, To, Ti, V, C, C);
+  ta.w = X.tw; ta.wb = bf(X.tw, wq); ta.out = X.h; ta.outb = bfa(X.h, hb); ta.bias = q.p(L.tcn_b);
+  ta.st_sum = X.bn2.fsum; ta.st_sq = X.bn2.fsq; ta.gap = X.gap;
+  if (F.top != OP_F32) {  // materialise u = relu(bn1(g)) once (also the tcn wgrad operand): bf16, or
+    // (bf16x3) rows [u_hi | u_lo] for the bf16 LDS-DMA implicit-GEMM kernels
+    BnReluArgs br;
+    std::memset(&br, 0, sizeof(br));
+    br.M = Mi; br.C = C; br.bn = bn1; br.g = X.g; br.u = X.u; br.g16 = hb; br.x3 = x3;
+    F3_TRY(f3_bnrelu_bf16(&br, s));
+    set_in(ta, X.u, C, F.top);
+    ta.zero = w.zero;
+    F3_TRY(f3_conv_gemm(&ta, 0, EPI_BIAS | EPI_STATS | EPI_GAP, s));
+  } else {
+    set_in(ta, X.g, C, OP_F32);
+    ta.pro_bn = bn1;
+    F3_TRY(f3_conv_gemm(&ta, 1, EPI_BIAS | EPI_STATS | EPI_GAP, s));
+  }
+  // channel attention (stgcan.py:59-74)
+  CaArgs ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.N = N; ca.C = C; ca.inv_tv = 1.f / (float)(To * V); ca.bn2 = bn2;
+  ca.bnca = q.ref(L.bnca, X.bnca, (float)N, eval);
+  ca.W1 = q.p(L.ca_w1); ca.b1 = q.p(L.ca_b1); ca.W2 = q.p(L.ca_w2); ca.b2 = q.p(L.ca_b2);
+  ca.gapsum = X.gap; ca.q1 = X.q1; ca.hid = X.hid; ca.att = X.att; ca.ca_sum = X.bnca.fsum; ca.ca_sq = X.bnca.fsq;
+  F3_TRY(f3_ca_fwd(&ca, s));
+  // residual add + ReLU (stgcan.py:143-144), pooled mean after the last block (stgcan.py:224)
+  BlockArgs ba;
+  std::memset(&ba, 0, sizeof(ba));
+  ba.N = N; ba.TV = To * V; ba.C = C; ba.res_kind = L.res; ba.inv_tv = 1.f / (float)(To * V);
+  ba.bn2 = bn2; ba.bnr = bnr; ba.h = X.h; ba.r = X.r; ba.x = X.x; ba.att = X.att; ba.out = X.out;
+  ba.pool = l == 6 ? W.pool : nullptr;
+  ba.part = W.detm;
+  ba.act16 = hb;
+  if (F.outb_w) { ba.outb = X.outb; ba.x3 = 1; }
+  F3_TRY(f3_block_out(ba, s));
+  if (train) {
+    add_bnrun(run, q, L.bn1, X.bn1.fsum, X.bn1.fsq, Mi);
+    add_bnrun(run, q, L.bn2, X.bn2.fsum, X.bn2.fsq, Mo);
+    if (L.res == RES_CONV) add_bnrun(run, q, L.bnr, X.bnr.fsum, X.bnr.fsq, Mo);
+    add_bnrun(run, q, L.bnca, X.bnca.fsum, X.bnca.fsq, N);
   }
   return F3_OK;
 }
@@ -788,7 +828,7 @@ int stream_forward_layer(const f3_net& net, int si, int N, int train, const Ptrs
 // The flat-parameter ranges of one skeleton layer: [gcn.conv.weight .. channel_attention ... 4.bias]
 // (contiguous: entries are laid out in creation order within a phase group, 16-B aligned) and its
 // edge_importance entry (created after the stream's layers).
-RmsRanges layer_ranges(const f3_net& n, const LayerIdx& L) {
+RmsRanges layer_ranges(const Net& n, const LayerIdx& L) {
   RmsRanges r;
   r.n = 2;
   const Entry &a = n.entries[L.gcn_w], &b = n.entries[L.ca_b2], &e = n.entries[L.edge];
@@ -809,283 +849,297 @@ bool debug_stop(int si, int l) {
   return a == si && b == l;
 }
 
-// Backward of layers l_hi..l_lo (descending); data_bn after layer 0. Layer l writes its
-// input gradient to W.dx[(6-l)&1] and reads layer l+1's from W.dx[(5-l)&1].
-// Main stream s: the chain that carries the input gradient down the layers. Side stream ss
-// (== s when not parallel): the layer's weight gradients (tcn / gcn / residual wgrad, gcn
-// bias + edge importance), which nothing downstream waits for. Layer l's side work starts after
-// ev_main[si][l]. It reads only
-// per-layer tensors, so the only side -> main edge is the final join. (Main also waiting on the side stream per layer — double-buffered scratch —
-// made HIP's stream-capture end fault on ROCm 7.2.)
-int stream_backward(const f3_net& net, int si, int N, const Ptrs& q, Ws& w, const float* skel, hipStream_t s,
-                    int l_hi, int l_lo, hipStream_t ss = nullptr, int call_hi = 6, int part = 3) {
-  if (!ss) ss = s;
-  (void)call_hi;
-  const bool split = ss != s;
+// The backward of block l of one skeleton stream has two halves. The main half, on the stream's own
+// queue s, carries the input gradient down the layers. The side half, on the weight-gradient queue ss
+// (== s when not parallel), computes what nothing downstream waits for: the tcn / gcn / residual
+// weight gradients, the gcn bias and edge importance. It starts after ev_main[si][l], recorded at the
+// end of the main half, and reads only per-layer tensors, so the only side -> main edge is the final
+// join. (Main also waiting on the side stream per layer - double-buffered scratch - made HIP's
+// stream-capture end fault on ROCm 7.2.)
+//
+// LayerCtx is what both halves need of one (stream, layer): built once by layer_ctx, read by both.
+struct LayerCtx {
+  const Net* net;
+  const Ptrs* q;
+  Ws* w;
+  int si, l, N;
+  bool split;  // the side half runs on another queue than the main half
+  int C, Ci, Ti, To, Mi, Mo;
+  BnRef bn1, bn2, bnr;
+  // layer l writes its input gradient to dx = W.dx[(6-l)&1] and reads layer l+1's, dout =
+  // W.dx[(5-l)&1] (none at l == 6: the pooled gradient)
+  float* dx;
+  const float* dout;
+  bool ca_sums;  // the block sums P1 / P2 / Q2 summed by ca_bwd1x from the partial rows
+  CaArgs ca;     // (wpart unset: the side half's weight kernel alone takes it)
+  // the gcn backward launch of the layer's route (main half) and the partial rows it leaves for the
+  // side half's column sums
+  Gcn0Args b0;
+  GcnDgradMixArgs gf;
+  MixArgs mx;
+  int g0_parts;   // GCN_FIRST: dA_eff / gcn weight gradient rows
+  int mix_parts;  // split, other routes: dA_eff rows
+};
+
+int layer_ctx(const Net& net, int si, int l, int N, const Ptrs& q, Ws& w, bool split, LayerCtx& c) {
   const StreamIdx& S = net.st[si];
   StreamWs& W = w.st[si];
+  const LayerIdx& L = S.L[l];
+  const LayerFmt& F = L.fmt;
+  LayerWs& X = W.L[l];
   const int K = net.K, V = net.V;
-  const int hb = net.cfg.precision == F3_PRECISION_BF16;
-  const int x3 = is_x3(net), wq = hb || x3;
-  const float* dout = l_hi == 6 ? nullptr : W.dx[(5 - l_hi) & 1];
-  int pp = (6 - l_hi) & 1;
-  for (int l = l_hi; l >= l_lo; --l) {
-    const LayerIdx& L = S.L[l];
-    LayerWs& X = W.L[l];
-    const int C = L.cout, Ci = L.cin, Ti = L.T_in, To = L.T_out;
-    const int Mi = N * Ti * V, Mo = N * To * V;
-    float* dx = W.dx[pp];
-    float* const dh = X.dh;
-    float* const dg = X.dg;
-    float* const dres = X.dres;
-    ColsumJob cj[kColsumJobs];  // side-queue column sums, launched together before the gcn bias step
-    int ncj = 0;
-    const BnRef bn1 = q.ref(L.bn1, X.bn1, (float)Mi, 0);
-    const BnRef bn2 = q.ref(L.bn2, X.bn2, (float)Mo, 0);
-    BnRef bnr;
-    std::memset(&bnr, 0, sizeof(bnr));
-    if (L.res == RES_CONV) bnr = q.ref(L.bnr, X.bnr, (float)Mo, 0);
-    BlockArgs ba;
-    std::memset(&ba, 0, sizeof(ba));
-    ba.N = N; ba.TV = To * V; ba.C = C; ba.res_kind = L.res; ba.inv_tv = 1.f / (float)(To * V);
-    ba.bn2 = bn2; ba.bnr = bnr; ba.h = X.h; ba.r = X.r; ba.x = X.x; ba.att = X.att; ba.out = X.out;
-    ba.dout = dout; ba.dout_nc = l == 6 ? W.dpool : nullptr; ba.act16 = hb;
-    ba.P1 = X.P1; ba.P2 = X.P2; ba.Q2 = X.Q2; ba.bnr_bsum = X.bnr.bsum; ba.bnr_bsq = X.bnr.bsq;
-    ba.bn2_bsum = X.bn2.bsum; ba.bn2_bsq = X.bn2.bsq; ba.e = X.e; ba.dh = dh;
-    ba.dres = L.res == RES_CONV ? dres : (L.res == RES_ID ? dx : nullptr);
-    ba.dhb = bfa(dh, hb || x3);  // bf16x3: dh as split hi / lo planes (the tcn dgrad / wgrad operand)
-    ba.x3 = x3;
-    ba.dresb = L.res == RES_CONV ? bfa(dres, hb || x3) : nullptr;  // bf16x3: [hi | lo] rows
-    ba.dgamma2 = q.g(L.bn2.w); ba.dbeta2 = q.g(L.bn2.b);
-    if (L.res == RES_CONV) { ba.dgammar = q.g(L.bnr.w); ba.dbetar = q.g(L.bnr.b); }
-    ba.part = W.detm;
-    // the block sums P1 / P2 / Q2 summed by ca_bwd1x from the partial rows (one launch less per layer)
-    const bool ca_sums = f3_ca_x_ok(N, C, To * V);
-    ba.no_colsum = ca_sums;
-    if (part & 1) F3_TRY(f3_block_bwd_reduce(ba, s));
-    ba.no_colsum = 0;
-    ba.dbpart = x3 ? X.dbpart : nullptr;  // (block_bwd_apply only: the bias-gradient rows)
-    CaArgs ca;
-    std::memset(&ca, 0, sizeof(ca));
-    ca.N = N; ca.C = C; ca.inv_tv = 1.f / (float)(To * V); ca.bn2 = bn2;
-    ca.bnca = q.ref(L.bnca, X.bnca, (float)N, 0);
-    ca.W1 = q.p(L.ca_w1); ca.b1 = q.p(L.ca_b1); ca.W2 = q.p(L.ca_w2); ca.b2 = q.p(L.ca_b2);
-    ca.gapsum = X.gap; ca.q1 = X.q1; ca.hid = X.hid; ca.att = X.att; ca.ca_sum = X.bnca.fsum; ca.ca_sq = X.bnca.fsq;
-    ca.P1 = X.P1; ca.P2 = X.P2; ca.dq2 = X.dq2; ca.dbn = X.dbn; ca.dq1 = X.dq1; ca.e = X.e;
-    ca.Q2 = X.Q2; ca.bnr_bsum = L.res == RES_CONV ? X.bnr.bsum : nullptr; ca.bnr_bsq = L.res == RES_CONV ? X.bnr.bsq : nullptr;
-    ca.bn2_bsum = X.bn2.bsum; ca.bn2_bsq = X.bn2.bsq;
-    ca.g_bnca_gamma = q.g(L.bnca.w); ca.g_bnca_beta = q.g(L.bnca.b);
-    ca.g_b1 = q.g(L.ca_b1); ca.g_W1 = q.g(L.ca_w1); ca.g_W2 = q.g(L.ca_w2); ca.g_b2 = q.g(L.ca_b2);
-    if (ca_sums) { ca.bpart = W.detm; ca.bchunks = f3_block_chunks(To * V); }
-    if (part & 1) F3_TRY(f3_ca_bwd(&ca, s));  // the W1/W2 gradients (ca_bwd_w) go to the side stream
-    if (part & 1) F3_TRY(f3_block_bwd_apply(ba, s));
-    // (Starting the tcn / residual / CA weight gradients right after block_bwd_apply instead of after
-    // the layer's whole main chain measured slower, 5.69 vs 5.54 ms/step, profiles/r03_side_early_ab.txt:
-    // the side work then takes CUs from the main chain, the step's critical path.)
-    // tcn input gradient (transposed conv) with ReLU mask + BN1-backward sums
-    ConvGemmArgs td;
-    std::memset(&td, 0, sizeof(td));
-    td.g = geom(Mi, C, C, 9, L.stride, 4, 1, Ti, To, V, C, C);
-    td.in = (hb || x3) ? nullptr : dh; td.inb = bfa(dh, hb || x3); td.zero = w.zero;
-    td.w = X.twT; td.wb = bf(X.twT, wq); td.out = W.dv; td.aux = X.g; td.ldaux = C; td.epi_bn = bn1;
-    if (x3) x3_gemm(td, C);  // dh rows [hi | lo]
-    td.outb = bfa(W.dv, hb); td.auxb = hb ? reinterpret_cast<const unsigned short*>(X.g) : nullptr;
-    td.st_sum = X.bn1.bsum; td.st_sq = X.bn1.bsq;
-    if (part & 1) F3_TRY(f3_conv_gemm(&td, 0, EPI_RELUMASK, s));
-    if (debug_stop(si, l)) return F3_OK;
-    BnBwdArgs bb;
-    std::memset(&bb, 0, sizeof(bb));
-    bb.N = N; bb.TV = Ti * V; bb.C = C; bb.V = V; bb.bn = bn1; bb.bsum = X.bn1.bsum; bb.bsq = X.bn1.bsq;
-    bb.dgamma = q.g(L.bn1.w); bb.dbeta = q.g(L.bn1.b); bb.dv = W.dv; bb.g = X.g; bb.dg = dg; bb.G = X.G;
-    bb.Gpart = X.gpart; bb.dgb = bfa(dg, hb); bb.act16 = hb; bb.no_colsum = split;
-    const bool gcat = x3 && f3_mix_x3_ok(K, V, Ci);  // dg as [hi | lo] rows (see plan)
-    if (gcat) { bb.dgb = bfa(dg, 1); bb.x3 = 1; }
-    if (part & 1) F3_TRY(f3_bn_bwd_apply(bb, s));
-    // gcn: dZ = dg W^T ; dW ; mix^T ; bias/edge grads
-    const bool g0 = (hb || x3) && f3_gcn0_ok(K, V, Ci, C);  // the 3-channel first block (layer0.hip)
-    Gcn0Args b0;
-    std::memset(&b0, 0, sizeof(b0));
-    int g0_parts = 0;
-    if (g0) {
-      b0.frames = N * Ti; b0.K = K; b0.V = V; b0.Ci = Ci; b0.A = X.aeff;
-      b0.x = reinterpret_cast<const unsigned short*>(X.x); b0.w = bf(X.gw, 1); b0.z = bfa(X.z, 1);
-      b0.dg = bfa(dg, 1); b0.dx = dx; b0.accumulate = L.res == RES_ID;
-      b0.f32 = x3;  // bf16x3: fp32 x / w / Z / dg
-      g0_parts = f3_gcn0_bwd_parts(&b0);
-      if ((size_t)g0_parts * (K * V * V + K * C * Ci) > (size_t)kMixParts * K * V * V) return F3_EINVAL;
-      b0.part_dA = X.mixpart;
-      b0.part_dW = X.mixpart + (size_t)g0_parts * K * V * V;
-    }
-    ConvGemmArgs gd;
-    std::memset(&gd, 0, sizeof(gd));
-    gd.g = geom(Mi, K * Ci, C, 1, 1, 0, 0, Ti, Ti, V, C, K * Ci);
-    gd.in = hb ? nullptr : dg; gd.inb = bfa(dg, hb); gd.zero = w.zero;
-    gd.w = X.gwT; gd.wb = bf(X.gwT, wq); gd.x3 = x3; gd.out = W.dZ;
-    if (gcat) {  // dg rows [hi | lo]
-      gd.x3 = 0; gd.in = nullptr; gd.inb = bfa(dg, 1);
-      x3_gemm(gd, C);
-    }
-    const bool dzb = hb && f3_mix_lds_ok(K, V, Ci);  // bf16 dZ feeds the LDS graph-mix backward
-    if (dzb) {
-      if (!f3_igemm_ok(gd)) return F3_EINVAL;
-      gd.outb = bfa(W.dZ, 1);
-    }
-    // bf16x3: dZ, dx and dA in one pass over dg and x (gcn_bwd.hip), dZ never in HBM. Ci = 64 only:
-    // there the fused kernel makes the pair's sums in the pair's order (one channel chunk, the mix
-    // backward's frame-to-row map below), so the step's results are the same bits. With Ci / 64 chunks
-    // in separate workgroups dA would be summed in another order, and RMSprop turns last-bit gradient
-    // differences into different trajectories within a few steps.
-    const bool gfuse = gcat && !g0 && Ci == 64 && gcn_dgrad_fused() && f3_gcn_dgrad_mix_ok(K, V, Ci, C);
-    GcnDgradMixArgs gf;
-    std::memset(&gf, 0, sizeof(gf));
-    if (gfuse) {
-      gf.frames = N * Ti; gf.K = K; gf.V = V; gf.Cin = Ci; gf.C = C; gf.dg = bfa(dg, 1); gf.w = bf(X.gwT, 1);
-      gf.A = X.aeff; gf.x = X.x; gf.dx = dx; gf.dA = X.dAeff; gf.accumulate = L.res == RES_ID;
-      gf.part = X.mixpart; gf.no_colsum = split;
-    }
-    if ((part & 1) && !g0 && !gfuse) F3_TRY(f3_conv_gemm(&gd, 0, 0, s));
-    MixArgs mx;
-    std::memset(&mx, 0, sizeof(mx));
-    mx.K = K; mx.V = V; mx.Cin = Ci; mx.frames = N * Ti; mx.A = X.aeff; mx.x = X.x; mx.z = W.dZ;
-    mx.dx = dx; mx.dA = X.dAeff; mx.accumulate = L.res == RES_ID; mx.part = X.mixpart; mx.x16 = hb;
-    mx.no_colsum = split; mx.x3 = x3;
-    mx.dzb = dzb ? bfa(W.dZ, 1) : nullptr;
-    if (gfuse) gf.max_workgroups = f3_mix_bwd_parts(&mx);  // row r: frames r, r + rows, ... as mix_bwd_x3
-    if (part & 1) F3_TRY(g0 ? f3_gcn0_bwd(&b0, s) : gfuse ? f3_gcn_dgrad_mix(&gf, s) : f3_mix_bwd(&mx, s));
-    if (L.res == RES_CONV) {
-      ConvGemmArgs rd;
-      std::memset(&rd, 0, sizeof(rd));
-      rd.g = geom(Mi, Ci, C, 1, L.stride, 0, 1, Ti, To, V, C, Ci);
-      rd.in = hb ? nullptr : dres; rd.inb = bfa(dres, hb); rd.zero = w.zero;
-      rd.w = X.rwT; rd.wb = bf(X.rwT, wq); rd.x3 = x3; rd.out = dx;
-      if (x3) {  // dres rows [hi | lo]
-        rd.x3 = 0; rd.in = nullptr; rd.inb = bfa(dres, 1);
-        x3_gemm(rd, C);
-      }
-      if (part & 1) F3_TRY(f3_conv_gemm(&rd, 0, EPI_ADD, s));
-    }
-    // ---- side stream: this layer's weight gradients ----
-    if (split && (part & 1) && hipEventRecord(net.ev_main[si][l], s) != hipSuccess) return F3_EHIP;
-    if (split && (part & 2) && hipStreamWaitEvent(ss, net.ev_main[si][l], 0) != hipSuccess) return F3_EHIP;
-    WgradArgs tw;
-    std::memset(&tw, 0, sizeof(tw));
-    tw.wg_pct = side_pct(split, l);
-    tw.g = geom(Mo, C, C, 9, L.stride, 4, 0, To, Ti, V, C, C);
-    tw.ldy = C; tw.dw = q.g(L.tcn_w); tw.db = q.g(L.tcn_b);
-    tw.outmap = WG_OUT_CONV; tw.bf16 = hb; tw.x3 = x3;
-    if (hb) {  // bf16 operands dh, u; split partials in the stream's slab, summed into the grads
-      tw.dyb = bfa(dh, 1); tw.inb = X.u; tw.zero = w.zero;
-      tw.slab = W.slab; tw.slab_cap = kWgradSlabFloats; tw.dw_ref = q.g(L.tcn_w);
-      if (!f3_wgrad_glds_ok(tw)) return F3_EINVAL;
-      if (part & 2) F3_TRY(f3_conv_wgrad(&tw, 0, ss));
-    } else if (x3) {  // on the bf16 kernels over the [hi | lo] rows of dh and u: three row segments
-      // (dh_hi u_hi, dh_lo u_hi, dh_hi u_lo). (One GEMM on [dh_hi | dh_lo] x [u_hi | u_lo] whose
-      // quadrants a fold adds computes the unused lo*lo quadrant too: 11.31 vs 10.78 ms/step.)
-      tw.x3 = 0; tw.bf16 = 1;
-      tw.ldy = 2 * C; tw.dyb = bfa(dh, 1); tw.inb = X.u; tw.zero = w.zero;
-      tw.slab = W.slab; tw.slab_cap = kWgradSlabFloats * 4; tw.dw_ref = q.g(L.tcn_w);
-      tw.g = geom(Mo, C, C, 9, L.stride, 4, 0, To, Ti, V, 2 * C, C);
-      tw.x3seg = 1;
-      tw.db = nullptr;  // the bias gradient from block_bwd_apply's dh rows (colsum below)
-      if (!f3_wgrad_glds_ok(tw)) return F3_EINVAL;
-      if (part & 2) F3_TRY(f3_conv_wgrad(&tw, 0, ss));
-      if (part & 2) {
-        const int rows = f3_block_chunks(To * V) * N;
-        cj[ncj++] = {X.dbpart, q.g(L.tcn_b), 2LL * C, rows, C};
-        if (L.res == RES_CONV) cj[ncj++] = {X.dbpart + C, q.g(L.res_b), 2LL * C, rows, C};
-      }
-    } else {
-      tw.dy = dh; tw.in = X.g; tw.pro_bn = bn1;
-      if (part & 2) F3_TRY(f3_conv_wgrad(&tw, 1, ss));
-    }
-    ca.wpart = W.dets;
-    if (part & 2) F3_TRY(f3_ca_bwd_weights(&ca, ss, cj, &ncj));
-    if (L.res == RES_CONV) {
-      WgradArgs rw;
-      std::memset(&rw, 0, sizeof(rw));
-      rw.wg_pct = side_pct(split, l);
-      rw.g = geom(Mo, C, Ci, 1, L.stride, 0, 0, To, Ti, V, Ci, C);
-      rw.ldy = C; rw.dw = q.g(L.res_w); rw.db = q.g(L.res_b); rw.outmap = WG_OUT_CONV; rw.bf16 = hb; rw.x3 = x3;
-      if (hb) {
-        rw.dyb = bfa(dres, 1); rw.inb = X.xb; rw.zero = w.zero;
-        rw.slab = W.slab; rw.slab_cap = kWgradSlabFloats; rw.dw_ref = q.g(L.res_w);
-      } else if (x3) {  // row segments as the tcn's
-        rw.x3 = 0; rw.bf16 = 1;
-        rw.ldy = 2 * C; rw.dyb = bfa(dres, 1); rw.inb = X.xb; rw.zero = w.zero;
-        rw.slab = W.slab; rw.slab_cap = kWgradSlabFloats * 4; rw.dw_ref = q.g(L.res_w);
-        rw.g = geom(Mo, C, Ci, 1, L.stride, 0, 0, To, Ti, V, 2 * Ci, C);
-        rw.x3seg = 1;
-        rw.db = nullptr;  // summed from block_bwd_apply's dres rows with the tcn bias
-        if (!f3_wgrad_glds_ok(rw)) return F3_EINVAL;
-      } else {
-        rw.dy = dres; rw.in = X.x;
-      }
-      if (part & 2) F3_TRY(f3_conv_wgrad(&rw, 0, ss));
-    }
-    if (split) {  // reductions whose results only feed weight gradients
-      const int T = L.T_in, fch = f3_bn_bwd_parts(N, T * V, V);
-      if (part & 2) cj[ncj++] = {X.gpart, X.G, (long long)V * C, fch, V * C};
-      const int mparts = g0 ? 0 : gfuse ? f3_gcn_dgrad_mix_parts(&gf) : f3_mix_bwd_parts(&mx);
-      if (mparts && (part & 2)) cj[ncj++] = {X.mixpart, X.dAeff, (long long)K * V * V, mparts, K * V * V};
-    }
-    if (g0 && (part & 2)) {  // the first block's dA_eff and gcn weight gradient partial rows
-      cj[ncj++] = {b0.part_dA, X.dAeff, (long long)K * V * V, g0_parts, K * V * V};
-      cj[ncj++] = {b0.part_dW, q.g(L.gcn_w), (long long)K * C * Ci, g0_parts, K * C * Ci};
-    }
-    // this layer's side-queue column sums (attention weights, tcn / residual biases, BN G, dA_eff,
-    // layer-0 gcn rows) as one launch; each job's summation order is that of its own f3_colsum
-    if (ncj > kColsumJobs) return F3_EINVAL;
-    F3_TRY(f3_colsum_multi(cj, ncj, ss));
-    ncj = 0;
-    WgradArgs gw;
-    std::memset(&gw, 0, sizeof(gw));
-    gw.wg_pct = side_pct(split, l);
-    gw.g = geom(Mi, C, K * Ci, 1, 1, 0, 0, Ti, Ti, V, K * Ci, C);
-    gw.ldy = C; gw.dw = q.g(L.gcn_w); gw.db = nullptr;
-    if (hb) {
-      gw.dyb = bfa(dg, 1); gw.inb = bfa(X.z, 1); gw.zero = w.zero;
-    } else {
-      gw.dy = dg; gw.in = X.z;
-    }
-    gw.outmap = WG_OUT_GCN; gw.gcn_cin = Ci; gw.bf16 = hb; gw.x3 = x3;
-    if (gcat) {  // row segments into the slab, reduced into the gcn layout
-      gw.x3 = 0; gw.bf16 = 1; gw.outmap = WG_OUT_CONV;
-      gw.ldy = 2 * C; gw.dyb = bfa(dg, 1); gw.inb = bfa(X.z, 1); gw.zero = w.zero; gw.dy = nullptr; gw.in = nullptr;
-      gw.slab = W.slab; gw.slab_cap = kWgradSlabFloats * 4; gw.dw_ref = q.g(L.gcn_w); gw.dw = nullptr;
-      gw.g = geom(Mi, C, K * Ci, 1, 1, 0, 0, Ti, Ti, V, 2 * K * Ci, C);
-      gw.x3seg = 1;
-      if (!f3_wgrad_glds_ok(gw)) return F3_EINVAL;
-    }
-    if ((part & 2) && !g0) F3_TRY(f3_conv_wgrad(&gw, 0, ss));
-    GcnBiasBwdArgs gb;
-    gb.K = K; gb.V = V; gb.C = C; gb.Aeff = X.aeff; gb.A = W.A; gb.G = X.G; gb.bias = q.p(L.gcn_b);
-    gb.db = q.g(L.gcn_b); gb.dAeff = X.dAeff; gb.dE = q.g(L.edge);
-    if (part & 2) F3_TRY(f3_gcn_bias_bwd(&gb, ss));
-    // fused optimizer: every gradient of this layer is final here on ss (its main-chain parts were
-    // waited for through ev_main), and nothing later in the backward reads these parameters
-    if (q.opt_gen && (part & 2))
-      F3_TRY(f3_optim_ranges(*q.opt_gen, layer_ranges(net, L), ss));
-    else if (q.opt_p && (part & 2))
-      F3_TRY(f3_rmsprop_ranges(q.opt_p, q.opt_sq, q.G, layer_ranges(net, L), q.lr, q.alpha, q.eps, 1.f, ss));
-    dout = dx;
-    pp ^= 1;
+  const int hb = is_bf16(net), x3 = is_x3(net);
+  c.net = &net; c.q = &q; c.w = &w; c.si = si; c.l = l; c.N = N; c.split = split;
+  const int C = c.C = L.cout, Ci = c.Ci = L.cin, Ti = c.Ti = L.T_in, To = c.To = L.T_out;
+  c.Mi = N * Ti * V;
+  c.Mo = N * To * V;
+  c.dx = W.dx[(6 - l) & 1];
+  c.dout = l == 6 ? nullptr : W.dx[(5 - l) & 1];
+  c.bn1 = q.ref(L.bn1, X.bn1, (float)c.Mi, 0);
+  c.bn2 = q.ref(L.bn2, X.bn2, (float)c.Mo, 0);
+  std::memset(&c.bnr, 0, sizeof(c.bnr));
+  if (L.res == RES_CONV) c.bnr = q.ref(L.bnr, X.bnr, (float)c.Mo, 0);
+  c.ca_sums = f3_ca_x_ok(N, C, To * V);
+  CaArgs& ca = c.ca;
+  std::memset(&ca, 0, sizeof(ca));
+  ca.N = N; ca.C = C; ca.inv_tv = 1.f / (float)(To * V); ca.bn2 = c.bn2;
+  ca.bnca = q.ref(L.bnca, X.bnca, (float)N, 0);
+  ca.W1 = q.p(L.ca_w1); ca.b1 = q.p(L.ca_b1); ca.W2 = q.p(L.ca_w2); ca.b2 = q.p(L.ca_b2);
+  ca.gapsum = X.gap; ca.q1 = X.q1; ca.hid = X.hid; ca.att = X.att; ca.ca_sum = X.bnca.fsum; ca.ca_sq = X.bnca.fsq;
+  ca.P1 = X.P1; ca.P2 = X.P2; ca.dq2 = X.dq2; ca.dbn = X.dbn; ca.dq1 = X.dq1; ca.e = X.e;
+  ca.Q2 = X.Q2; ca.bnr_bsum = L.res == RES_CONV ? X.bnr.bsum : nullptr; ca.bnr_bsq = L.res == RES_CONV ? X.bnr.bsq : nullptr;
+  ca.bn2_bsum = X.bn2.bsum; ca.bn2_bsq = X.bn2.bsq;
+  ca.g_bnca_gamma = q.g(L.bnca.w); ca.g_bnca_beta = q.g(L.bnca.b);
+  ca.g_b1 = q.g(L.ca_b1); ca.g_W1 = q.g(L.ca_w1); ca.g_W2 = q.g(L.ca_w2); ca.g_b2 = q.g(L.ca_b2);
+  if (c.ca_sums) { ca.bpart = W.detm; ca.bchunks = f3_block_chunks(To * V); }
+  // gcn backward: dZ = dg W^T, mix^T (dx, dA_eff)
+  Gcn0Args& b0 = c.b0;
+  std::memset(&b0, 0, sizeof(b0));
+  c.g0_parts = 0;
+  if (F.bwd == GCN_FIRST) {
+    b0.frames = N * Ti; b0.K = K; b0.V = V; b0.Ci = Ci; b0.A = X.aeff;
+    b0.x = reinterpret_cast<const unsigned short*>(X.x); b0.w = bf(X.gw, 1); b0.z = bfa(X.z, 1);
+    b0.dg = bfa(X.dg, 1); b0.dx = c.dx; b0.accumulate = L.res == RES_ID;
+    b0.f32 = x3;  // bf16x3: fp32 x / w / Z / dg
+    c.g0_parts = f3_gcn0_bwd_parts(&b0);
+    if ((size_t)c.g0_parts * (K * V * V + K * C * Ci) > (size_t)kMixParts * K * V * V) return F3_EINVAL;
+    b0.part_dA = X.mixpart;
+    b0.part_dW = X.mixpart + (size_t)c.g0_parts * K * V * V;
   }
-  if (l_lo > 0) return F3_OK;
-  DataBnArgs d;
-  std::memset(&d, 0, sizeof(d));
-  d.N = N; d.T = S.T; d.V = V; d.C = S.cin; d.motion = S.motion; d.skel = skel;
-  d.bn = q.ref(S.dbn, W.dbn, (float)(N * S.T), 0);
-  d.dout = dout; d.dgamma = q.g(S.dbn.w); d.dbeta = q.g(S.dbn.b);
-  d.part = W.detm;
-  if (part & 1) {  // the coalesced single-pass data_bn gradient where its shape fits, else the per-channel one
-    const int st = f3_databn_bwd2(&d, s);
-    if (st == F3_EINVAL) F3_TRY(f3_databn_bwd(&d, s));
-    else if (st != F3_OK) return st;
+  GcnDgradMixArgs& gf = c.gf;
+  std::memset(&gf, 0, sizeof(gf));
+  if (F.bwd == GCN_FUSED) {
+    gf.frames = N * Ti; gf.K = K; gf.V = V; gf.Cin = Ci; gf.C = C; gf.dg = bfa(X.dg, 1); gf.w = bf(X.gwT, 1);
+    gf.A = X.aeff; gf.x = X.x; gf.dx = c.dx; gf.dA = X.dAeff; gf.accumulate = L.res == RES_ID;
+    gf.part = X.mixpart; gf.no_colsum = split;
   }
+  MixArgs& mx = c.mx;
+  std::memset(&mx, 0, sizeof(mx));
+  mx.K = K; mx.V = V; mx.Cin = Ci; mx.frames = N * Ti; mx.A = X.aeff; mx.x = X.x; mx.z = W.dZ;
+  mx.dx = c.dx; mx.dA = X.dAeff; mx.accumulate = L.res == RES_ID; mx.part = X.mixpart; mx.x16 = hb;
+  mx.no_colsum = split; mx.x3 = x3;
+  mx.dzb = F.dzb ? bfa(W.dZ, 1) : nullptr;
+  if (F.bwd == GCN_FUSED) gf.max_workgroups = f3_mix_bwd_parts(&mx);  // row r: frames r, r + rows, ... as mix_bwd_x3
+  c.mix_parts = !split || F.bwd == GCN_FIRST ? 0
+                : F.bwd == GCN_FUSED         ? f3_gcn_dgrad_mix_parts(&gf)
+                                             : f3_mix_bwd_parts(&mx);
   return F3_OK;
 }
 
-void sensor_args(const f3_net& net, int N, int train, const Ptrs& q, Ws& w, const float* sensor, LstmArgs& la,
+// Main half: block backward, channel attention, tcn / gcn / residual input gradients, in that order on s.
+int layer_backward_main(const LayerCtx& c, hipStream_t s) {
+  const Net& net = *c.net;
+  const Ptrs& q = *c.q;
+  Ws& w = *c.w;
+  StreamWs& W = w.st[c.si];
+  const LayerIdx& L = net.st[c.si].L[c.l];
+  const LayerFmt& F = L.fmt;
+  LayerWs& X = W.L[c.l];
+  const int K = net.K, V = net.V, N = c.N, l = c.l;
+  const int hb = is_bf16(net), x3 = is_x3(net), wq = hb || x3;
+  const int C = c.C, Ci = c.Ci, Ti = c.Ti, To = c.To, Mi = c.Mi;
+  float* const dx = c.dx;
+  BlockArgs ba;
+  std::memset(&ba, 0, sizeof(ba));
+  ba.N = N; ba.TV = To * V; ba.C = C; ba.res_kind = L.res; ba.inv_tv = 1.f / (float)(To * V);
+  ba.bn2 = c.bn2; ba.bnr = c.bnr; ba.h = X.h; ba.r = X.r; ba.x = X.x; ba.att = X.att; ba.out = X.out;
+  ba.dout = c.dout; ba.dout_nc = l == 6 ? W.dpool : nullptr; ba.act16 = hb;
+  ba.P1 = X.P1; ba.P2 = X.P2; ba.Q2 = X.Q2; ba.bnr_bsum = X.bnr.bsum; ba.bnr_bsq = X.bnr.bsq;
+  ba.bn2_bsum = X.bn2.bsum; ba.bn2_bsq = X.bn2.bsq; ba.e = X.e; ba.dh = X.dh;
+  ba.dres = L.res == RES_CONV ? X.dres : (L.res == RES_ID ? dx : nullptr);
+  ba.dhb = bfa(X.dh, F.top != OP_F32);  // bf16, or (bf16x3) [hi | lo] rows: the tcn dgrad / wgrad operand
+  ba.x3 = x3;
+  ba.dresb = L.res == RES_CONV ? bfa(X.dres, F.top != OP_F32) : nullptr;
+  ba.dgamma2 = q.g(L.bn2.w); ba.dbeta2 = q.g(L.bn2.b);
+  if (L.res == RES_CONV) { ba.dgammar = q.g(L.bnr.w); ba.dbetar = q.g(L.bnr.b); }
+  ba.part = W.detm;
+  ba.no_colsum = c.ca_sums;  // (one launch less per layer)
+  F3_TRY(f3_block_bwd_reduce(ba, s));
+  ba.no_colsum = 0;
+  ba.dbpart = x3 ? X.dbpart : nullptr;  // (block_bwd_apply only: the bias-gradient rows)
+  F3_TRY(f3_ca_bwd(&c.ca, s));  // the W1/W2 gradients (ca_bwd_w) go to the side half
+  F3_TRY(f3_block_bwd_apply(ba, s));
+  // (Starting the tcn / residual / CA weight gradients right after block_bwd_apply instead of after
+  // the layer's whole main chain measured slower, 5.69 vs 5.54 ms/step, profiles/r03_side_early_ab.txt:
+  // the side work then takes CUs from the main chain, the step's critical path.)
+  // tcn input gradient (transposed conv) with ReLU mask + BN1-backward sums
+  ConvGemmArgs td;
+  std::memset(&td, 0, sizeof(td));
+  td.g = geom(Mi, C, C, 9, L.stride, 4, 1, Ti, To, V, C, C);
+  set_in(td, X.dh, C, F.top);
+  td.zero = w.zero;
+  td.w = X.twT; td.wb = bf(X.twT, wq); td.out = W.dv; td.aux = X.g; td.ldaux = C; td.epi_bn = c.bn1;
+  td.outb = bfa(W.dv, hb); td.auxb = hb ? reinterpret_cast<const unsigned short*>(X.g) : nullptr;
+  td.st_sum = X.bn1.bsum; td.st_sq = X.bn1.bsq;
+  F3_TRY(f3_conv_gemm(&td, 0, EPI_RELUMASK, s));
+  if (debug_stop(c.si, l)) return F3_OK;
+  BnBwdArgs bb;
+  std::memset(&bb, 0, sizeof(bb));
+  bb.N = N; bb.TV = Ti * V; bb.C = C; bb.V = V; bb.bn = c.bn1; bb.bsum = X.bn1.bsum; bb.bsq = X.bn1.bsq;
+  bb.dgamma = q.g(L.bn1.w); bb.dbeta = q.g(L.bn1.b); bb.dv = W.dv; bb.g = X.g; bb.dg = X.dg; bb.G = X.G;
+  bb.Gpart = X.gpart; bb.dgb = bfa(X.dg, hb || F.gcat); bb.act16 = hb; bb.no_colsum = c.split;
+  bb.x3 = F.gcat;  // dg as [hi | lo] rows
+  F3_TRY(f3_bn_bwd_apply(bb, s));
+  if (F.bwd == GCN_FIRST) {
+    F3_TRY(f3_gcn0_bwd(&c.b0, s));
+  } else if (F.bwd == GCN_FUSED) {
+    F3_TRY(f3_gcn_dgrad_mix(&c.gf, s));
+  } else {
+    ConvGemmArgs gd;
+    std::memset(&gd, 0, sizeof(gd));
+    gd.g = geom(Mi, K * Ci, C, 1, 1, 0, 0, Ti, Ti, V, C, K * Ci);
+    set_in(gd, X.dg, C, F.gop);
+    gd.zero = w.zero;
+    gd.w = X.gwT; gd.wb = bf(X.gwT, wq); gd.out = W.dZ;
+    if (F.dzb) {  // bf16 dZ feeds the LDS graph-mix backward
+      if (!f3_igemm_ok(gd)) return F3_EINVAL;
+      gd.outb = bfa(W.dZ, 1);
+    }
+    F3_TRY(f3_conv_gemm(&gd, 0, 0, s));
+    F3_TRY(f3_mix_bwd(&c.mx, s));
+  }
+  if (L.res == RES_CONV) {
+    ConvGemmArgs rd;
+    std::memset(&rd, 0, sizeof(rd));
+    rd.g = geom(Mi, Ci, C, 1, L.stride, 0, 1, Ti, To, V, C, Ci);
+    set_in(rd, X.dres, C, F.top);
+    rd.zero = w.zero;
+    rd.w = X.rwT; rd.wb = bf(X.rwT, wq); rd.out = dx;
+    F3_TRY(f3_conv_gemm(&rd, 0, EPI_ADD, s));
+  }
+  if (c.split && hipEventRecord(net.ev_main[c.si][l], s) != hipSuccess) return F3_EHIP;
+  return F3_OK;
+}
+
+// Side half: this layer's weight gradients, the column sums that only feed them, and its fused
+// optimizer update, on ss.
+int layer_backward_side(const LayerCtx& c, hipStream_t ss) {
+  const Net& net = *c.net;
+  const Ptrs& q = *c.q;
+  Ws& w = *c.w;
+  StreamWs& W = w.st[c.si];
+  const LayerIdx& L = net.st[c.si].L[c.l];
+  const LayerFmt& F = L.fmt;
+  LayerWs& X = W.L[c.l];
+  const int K = net.K, V = net.V, N = c.N, l = c.l;
+  const int C = c.C, Ci = c.Ci, Ti = c.Ti, To = c.To, Mi = c.Mi, Mo = c.Mo;
+  const bool first = F.bwd == GCN_FIRST;
+  if (c.split && hipStreamWaitEvent(ss, net.ev_main[c.si][l], 0) != hipSuccess) return F3_EHIP;
+  ColsumJob cj[kColsumJobs];  // this half's column sums, launched together before the gcn bias step
+  int ncj = 0;
+  // tcn: operands dh and u = relu(bn1(g)) (fp32 mode: g through the BN1 + ReLU prologue)
+  WgradArgs tw;
+  std::memset(&tw, 0, sizeof(tw));
+  tw.wg_pct = side_pct(c.split, l);
+  tw.g = geom(Mo, C, C, 9, L.stride, 4, 0, To, Ti, V, C, C);
+  tw.ldy = C; tw.dw = q.g(L.tcn_w); tw.db = q.g(L.tcn_b);
+  tw.outmap = WG_OUT_CONV;
+  set_wgrad_ops(tw, X.dh, C, F.top == OP_F32 ? static_cast<const void*>(X.g) : X.u, C, F.top, w.zero, W.slab,
+                q.g(L.tcn_w));
+  if (F.top == OP_F32) tw.pro_bn = c.bn1;
+  if (F.top == OP_HILO) {  // the tcn / residual bias gradients from block_bwd_apply's dh / dres rows
+    tw.db = nullptr;
+    const int rows = f3_block_chunks(To * V) * N;
+    cj[ncj++] = {X.dbpart, q.g(L.tcn_b), 2LL * C, rows, C};
+    if (L.res == RES_CONV) cj[ncj++] = {X.dbpart + C, q.g(L.res_b), 2LL * C, rows, C};
+  }
+  if (F.top != OP_F32 && !f3_wgrad_glds_ok(tw)) return F3_EINVAL;
+  F3_TRY(f3_conv_wgrad(&tw, F.top == OP_F32, ss));
+  CaArgs ca = c.ca;
+  ca.wpart = W.dets;
+  F3_TRY(f3_ca_bwd_weights(&ca, ss, cj, &ncj));
+  if (L.res == RES_CONV) {
+    WgradArgs rw;
+    std::memset(&rw, 0, sizeof(rw));
+    rw.wg_pct = side_pct(c.split, l);
+    rw.g = geom(Mo, C, Ci, 1, L.stride, 0, 0, To, Ti, V, Ci, C);
+    rw.ldy = C; rw.dw = q.g(L.res_w); rw.db = q.g(L.res_b); rw.outmap = WG_OUT_CONV;
+    set_wgrad_ops(rw, X.dres, C, F.top == OP_F32 ? static_cast<const void*>(X.x) : X.xb, Ci, F.top, w.zero, W.slab,
+                  q.g(L.res_w));
+    if (F.top == OP_HILO) {
+      rw.db = nullptr;  // summed from block_bwd_apply's dres rows with the tcn bias
+      if (!f3_wgrad_glds_ok(rw)) return F3_EINVAL;
+    }
+    F3_TRY(f3_conv_wgrad(&rw, 0, ss));
+  }
+  if (c.split) {  // reductions whose results only feed weight gradients
+    cj[ncj++] = {X.gpart, X.G, (long long)V * C, f3_bn_bwd_parts(N, Ti * V, V), V * C};
+    if (c.mix_parts) cj[ncj++] = {X.mixpart, X.dAeff, (long long)K * V * V, c.mix_parts, K * V * V};
+  }
+  if (first) {  // the first block's dA_eff and gcn weight gradient partial rows
+    cj[ncj++] = {c.b0.part_dA, X.dAeff, (long long)K * V * V, c.g0_parts, K * V * V};
+    cj[ncj++] = {c.b0.part_dW, q.g(L.gcn_w), (long long)K * C * Ci, c.g0_parts, K * C * Ci};
+  }
+  // the column sums (attention weights, tcn / residual biases, BN G, dA_eff, layer-0 gcn rows) as one
+  // launch; each job's summation order is that of its own f3_colsum
+  if (ncj > kColsumJobs) return F3_EINVAL;
+  F3_TRY(f3_colsum_multi(cj, ncj, ss));
+  if (!first) {  // gcn: dW from dg and Z
+    WgradArgs gw;
+    std::memset(&gw, 0, sizeof(gw));
+    gw.wg_pct = side_pct(c.split, l);
+    gw.g = geom(Mi, C, K * Ci, 1, 1, 0, 0, Ti, Ti, V, K * Ci, C);
+    gw.ldy = C; gw.dw = q.g(L.gcn_w); gw.db = nullptr;
+    gw.outmap = WG_OUT_GCN; gw.gcn_cin = Ci;
+    // (only the [hi | lo] rows go through the slab)
+    set_wgrad_ops(gw, X.dg, C, X.z, K * Ci, F.gop, w.zero, F.gcat ? W.slab : nullptr, q.g(L.gcn_w));
+    if (F.gcat) {  // row segments into the slab, reduced into the gcn layout
+      gw.outmap = WG_OUT_CONV;
+      gw.dw = nullptr;
+      if (!f3_wgrad_glds_ok(gw)) return F3_EINVAL;
+    }
+    F3_TRY(f3_conv_wgrad(&gw, 0, ss));
+  }
+  GcnBiasBwdArgs gb;
+  gb.K = K; gb.V = V; gb.C = C; gb.Aeff = X.aeff; gb.A = W.A; gb.G = X.G; gb.bias = q.p(L.gcn_b);
+  gb.db = q.g(L.gcn_b); gb.dAeff = X.dAeff; gb.dE = q.g(L.edge);
+  F3_TRY(f3_gcn_bias_bwd(&gb, ss));
+  // fused optimizer: every gradient of this layer is final here on ss (its main-chain parts were
+  // waited for through ev_main), and nothing later in the backward reads these parameters
+  if (q.opt_gen)
+    F3_TRY(f3_optim_ranges(*q.opt_gen, layer_ranges(net, L), ss));
+  else if (q.opt_p)
+    F3_TRY(f3_rmsprop_ranges(q.opt_p, q.opt_sq, q.G, layer_ranges(net, L), q.lr, q.alpha, q.eps, 1.f, ss));
+  return F3_OK;
+}
+
+// data_bn backward, on the stream's main queue after block 0's main half (which wrote W.dx[0])
+int databn_backward(const Net& net, int si, int N, const Ptrs& q, Ws& w, const float* skel, hipStream_t s) {
+  const StreamIdx& S = net.st[si];
+  StreamWs& W = w.st[si];
+  DataBnArgs d;
+  std::memset(&d, 0, sizeof(d));
+  d.N = N; d.T = S.T; d.V = net.V; d.C = S.cin; d.motion = S.motion; d.skel = skel;
+  d.bn = q.ref(S.dbn, W.dbn, (float)(N * S.T), 0);
+  d.dout = W.dx[(6 - 0) & 1]; d.dgamma = q.g(S.dbn.w); d.dbeta = q.g(S.dbn.b);
+  d.part = W.detm;
+  // the coalesced single-pass data_bn gradient where its shape fits, else the per-channel one
+  const int st = f3_databn_bwd2(&d, s);
+  if (st == F3_EINVAL) return f3_databn_bwd(&d, s);
+  return st;
+}
+
+void sensor_args(const Net& net, int N, int train, const Ptrs& q, Ws& w, const float* sensor, LstmArgs& la,
                  SHeadArgs& sa, Conv1dArgs& c1, Conv1dArgs& c2) {
   const int Ts = net.cfg.sensor_frames;
   const int eval = !train;
@@ -1137,7 +1191,7 @@ void sensor_args(const f3_net& net, int N, int train, const Ptrs& q, Ws& w, cons
   }
 }
 
-void head_args(const f3_net& net, int N, const Ptrs& q, Ws& w, HeadArgs& h) {
+void head_args(const Net& net, int N, const Ptrs& q, Ws& w, HeadArgs& h) {
   std::memset(&h, 0, sizeof(h));
   h.N = N;
   h.C = net.cfg.num_class;
@@ -1173,7 +1227,7 @@ static unsigned branch_event_flags() { return hipEventDisableTiming | hipEventRe
 
 // Private branch streams, created on the first eager call (never during a capture: there the
 // branches stay on the caller's stream). F3_SERIAL=1 keeps everything on one stream.
-bool ensure_parallel(f3_net& n, hipStream_t s) {
+bool ensure_parallel(Net& n, hipStream_t s) {
   if (n.par_init) return n.par_ok;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
@@ -1201,7 +1255,7 @@ bool ensure_parallel(f3_net& n, hipStream_t s) {
 // forked-but-empty branch in a stream capture breaks HIP graph instantiation.
 enum : int { BR_MOTION = 1, BR_SENSOR = 2, BR_SIDE = 4 };
 struct Branches {
-  f3_net& n;
+  Net& n;
   hipStream_t s;
   bool par;
   int mask = BR_MOTION | BR_SENSOR | BR_SIDE;
@@ -1253,13 +1307,205 @@ struct Branches {
 
 // stream `t` waits for everything backward phase 1 queued (no-op after a serial phase 1, whose
 // work is all on the caller's stream)
-int wait_phase1(f3_net& n, hipStream_t t) {
+int wait_phase1(Net& n, hipStream_t t) {
   for (int i = 0; i < 4; ++i)
     if ((n.p1_mask >> i & 1) && hipStreamWaitEvent(t, n.ev_p1[i], 0) != hipSuccess) return F3_EHIP;
   return F3_OK;
 }
 
+struct FusedOpt {
+  float *p, *sq;
+  float lr, alpha, eps;
+  const OptLaunch* gen = nullptr;  // f3_net_backward_optim
+};
+
+// the skeleton layers' ranges cover exactly their own parameter entries (the fused optimizer's
+// per-layer launches rely on it; checked once per call, ~300 entries)
+bool layer_ranges_ok(const Net& n) {
+  for (int si = 0; si < n.nstreams; ++si)
+    for (int l = 0; l < 7; ++l) {
+      const LayerIdx& L = n.st[si].L[l];
+      const RmsRanges r = layer_ranges(n, L);
+      long long sum = 0;
+      for (int i = L.gcn_w; i <= L.ca_b2; ++i) {
+        const Entry& e = n.entries[i];
+        if (e.kind != F3_ENTRY_PARAM) continue;
+        if (e.offset < r.lo[0] || e.offset >= r.lo[0] + r.len[0]) return false;
+        sum += (e.numel + 3) / 4 * 4;
+      }
+      if (sum != r.len[0]) return false;
+    }
+  return true;
+}
+
+// f3_net_backward_rmsprop's plan: whether the per-layer updates apply (a layout whose layer entries are
+// not contiguous cannot be updated per layer) and the leftover ranges updated after the join
+void fused_opt_plan(Net& n) {
+  n.fused_opt = layer_ranges_ok(n);
+  n.rest_ranges.clear();
+  n.rest_ranges_opt.clear();
+  // the no-gradient entries (whole padded entries, adjacent ones merged) for the flat update
+  n.nograd_skip.n = 0;
+  for (const Entry& e : n.entries) {
+    if (e.kind != F3_ENTRY_PARAM || !e.nograd) continue;
+    OptSkip& k = n.nograd_skip;
+    const long long lo = e.offset, len = (e.numel + 3) / 4 * 4;
+    if (k.n && k.lo[k.n - 1] + k.len[k.n - 1] == lo) k.len[k.n - 1] += len;
+    else if (k.n < kOptSkip) { k.lo[k.n] = lo; k.len[k.n] = len; ++k.n; }
+    else { n.nograd_skip.n = -1; break; }  // more ranges than the kernel takes: f3_net_backward_optim refuses
+  }
+  if (!n.fused_opt) return;
+  std::vector<std::pair<long long, long long>> done, rest, rest_opt;
+  for (int si = 0; si < n.nstreams; ++si)
+    for (int l = 0; l < 7; ++l) {
+      const RmsRanges r = layer_ranges(n, n.st[si].L[l]);
+      for (int j = 0; j < r.n; ++j) done.push_back({r.lo[j], r.lo[j] + r.len[j]});
+    }
+  for (const Entry& e : n.entries) {
+    if (e.kind != F3_ENTRY_PARAM) continue;
+    bool in = false;
+    for (auto& d : done) in = in || (e.offset >= d.first && e.offset < d.second);
+    if (in) continue;
+    const long long lo = e.offset, hi = e.offset + (e.numel + 3) / 4 * 4;
+    if (!rest.empty() && rest.back().second == lo) rest.back().second = hi;
+    else rest.push_back({lo, hi});
+    if (e.nograd) continue;
+    if (!rest_opt.empty() && rest_opt.back().second == lo) rest_opt.back().second = hi;
+    else rest_opt.push_back({lo, hi});
+  }
+  auto pack = [](const std::vector<std::pair<long long, long long>>& v, std::vector<RmsRanges>& out) {
+    RmsRanges r;
+    r.n = 0;
+    for (size_t i = 0; i < v.size(); ++i) {
+      r.lo[r.n] = v[i].first;
+      r.len[r.n] = v[i].second - v[i].first;
+      if (++r.n == kRmsRanges || i + 1 == v.size()) {
+        out.push_back(r);
+        r.n = 0;
+      }
+    }
+  };
+  pack(rest, n.rest_ranges);
+  pack(rest_opt, n.rest_ranges_opt);
+}
+
+int net_backward(Net* net, int N, const float* params, const float* dout, float* grads, void* workspace, int phase,
+                 void* stream, const FusedOpt* opt) {
+  if (!net || !params || !grads || !workspace || N < 2 || phase < 0 || phase > 2) return F3_EINVAL;
+  if (phase != 2 && !dout) return F3_EINVAL;
+  F3_TRY(net->cstatus.take(false));
+  if (opt && phase != 0) return F3_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  Ws w = plan(*net, N, (char*)workspace);
+  Ptrs q{*net, params, nullptr, nullptr, grads};
+  if (opt) {
+    q.opt_p = opt->p; q.opt_sq = opt->sq; q.lr = opt->lr; q.alpha = opt->alpha; q.eps = opt->eps;
+    q.opt_gen = opt->gen;
+  }
+  // The skeleton streams' layers l_hi..l_lo, the two streams interleaved (see layer_forward).
+  // after_first: called once the first layer's main halves are submitted (the sensor backward, so its
+  // host submission does not hold back the skeleton streams' first layer).
+  // Parallel mode (the side queue differs): main(l) of both streams, then side(l + 1) of both. Each
+  // layer's main halves are submitted before the previous layer's side halves (the weight gradients):
+  // the host can be held up submitting to the long side queue, and the main queues should already hold
+  // their next layer by then (neutral in time since the side split, kept: it removed 150-490 us idle
+  // stretches of the main queues before it). Serial mode (F3_SERIAL, or under capture before the
+  // private queues exist): main(l) then side(l), stream by stream.
+  // data_bn's backward follows block 0 on the stream's main queue: right after main(0) in the parallel
+  // mode, after side(0) in the serial mode. It needs only main(0)'s dx; the two positions are the
+  // orders the step has always issued, kept as they are.
+  // Every layer's weight gradients run on the side queues. (A former F3_TAIL_SIDE=0 option ran
+  // layer 0's on the stream's own queue: measured neutral to 1 % slower, and it raced with the
+  // side queue's layer-1 launch on the stream's shared split-K slab, so it is gone.)
+  LayerCtx cx[2][7];
+  auto skeleton = [&](Branches& br, int l_hi, int l_lo, auto after_first) -> int {
+    const bool defer = br.side() != br.s;
+    const int ns = net->nstreams;
+    for (int l = l_hi; l >= l_lo; --l) {
+      for (int si = 0; si < ns; ++si) {
+        F3_TRY(layer_ctx(*net, si, l, N, q, w, br.side(si) != br.at(si), cx[si][l]));
+        F3_TRY(layer_backward_main(cx[si][l], br.at(si)));
+        if (debug_stop(si, l)) return F3_OK;  // leave the scratch as is for f3_net_debug_tensor
+        if (!defer) F3_TRY(layer_backward_side(cx[si][l], br.side(si)));
+        if (l == 0) F3_TRY(databn_backward(*net, si, N, q, w, w.skel, br.at(si)));
+      }
+      if (l == l_hi) F3_TRY(after_first());
+      if (defer && l < l_hi)
+        for (int si = 0; si < ns; ++si) F3_TRY(layer_backward_side(cx[si][l + 1], br.side(si)));
+    }
+    if (defer)
+      for (int si = 0; si < ns; ++si) F3_TRY(layer_backward_side(cx[si][l_lo], br.side(si)));
+    return F3_OK;
+  };
+  if (phase == 2) {
+    Branches br{*net, s, ensure_parallel(*net, s)};
+    // the same queue assignment as phase 1 (mask incl. the sensor queue, which carries the motion
+    // stream's weight gradients): a stream's split-K slab is then only ever used from one queue,
+    // so phase 2's weight gradients cannot overlap phase 1's still-draining ones on that slab
+    br.mask = (net->nstreams > 1 ? BR_MOTION : 0) | (net->has_sensor ? BR_SENSOR : 0) |
+              (net->nstreams > 0 ? BR_SIDE : 0);
+    F3_TRY(br.fork());
+    F3_TRY(skeleton(br, kSplitLayer - 1, 0, [] { return (int)F3_OK; }));
+    F3_TRY(br.join());
+    F3_TRY(wait_phase1(*net, s));  // phase 1's queues (e.g. the sensor queue) are done too
+    net->p1_mask = 0;
+    return F3_OK;
+  }
+  // the gradient buffer and the backward's zeroed workspace block: one launch when both are float
+  // ranges on 16-byte boundaries (the usual case), else two memsets
+  const size_t zb = w.zb1 - w.zb0;
+  if (zb % 4 == 0 && ((uintptr_t)grads | (uintptr_t)w.zb0) % 16 == 0) {
+    F3_TRY(f3_zero2(grads, net->nparam, reinterpret_cast<float*>(w.zb0), (long long)(zb / 4), s));
+  } else {
+    if (hipMemsetAsync(grads, 0, sizeof(float) * net->nparam, s) != hipSuccess) return F3_EHIP;
+    if (hipMemsetAsync(w.zb0, 0, zb, s) != hipSuccess) return F3_EHIP;
+  }
+  HeadArgs h;
+  head_args(*net, N, q, w, h);
+  h.g_out = dout;
+  LstmArgs la;
+  SHeadArgs sa;
+  Conv1dArgs c1, c2;
+  if (net->has_sensor) sensor_args(*net, N, 1, q, w, w.sensor, la, sa, c1, c2);
+  if (net->cfg.model == F3_MODEL_BILSTM) {
+    sa.dout = dout;
+    sa.dout_ld = net->cfg.num_class;
+  } else {
+    F3_TRY(f3_head_bwd_data(&h, s));  // dlogits + feature gradients: what the streams' backward waits for
+  }
+  Branches br{*net, s, ensure_parallel(*net, s)};
+  br.mask = (net->nstreams > 1 ? BR_MOTION : 0) | (net->has_sensor ? BR_SENSOR : 0) | (net->nstreams > 0 ? BR_SIDE : 0);
+  F3_TRY(br.fork());
+  // the head Linear's weight gradients off the critical path, at the front of the side queue (which
+  // then waits for the first layer's data gradients anyway)
+  if (net->cfg.model != F3_MODEL_BILSTM) F3_TRY(f3_head_bwd_weight(&h, br.side()));
+  auto sensor_bwd = [&]() -> int {
+    if (!net->has_sensor) return F3_OK;
+    const hipStream_t ss = br.at(2);
+    F3_TRY(f3_shead_bwd(&sa, ss));
+    F3_TRY(f3_lstm_bwd(&la, ss));
+    if (net->has_cnn) {
+      const CnnCoop coop{w.cpart, w.csyncb};
+      net->smark(2, ss);
+      F3_TRY(f3_cnn1d_bwd(&c1, &c2, &coop, ss));
+      net->smark(3, ss);
+      F3_TRY(net->cstatus.post(w.csyncb, ss));
+    }
+    return F3_OK;
+  };
+  // the skeleton streams' first layer is submitted before the sensor backward; a sensor-only model has
+  // no skeleton layer to wait for
+  if (net->nstreams == 0) F3_TRY(sensor_bwd());
+  else F3_TRY(skeleton(br, 6, phase == 1 ? kSplitLayer : 0, sensor_bwd));
+  if (phase == 1) return br.mark_phase1();  // the caller orders its all-reduce after f3_net_wait_phase1
+  F3_TRY(br.join());
+  return F3_OK;
+}
+
 }  // namespace
+
+// the C ABI's opaque handle (fall3.h) is the Net above
+struct f3_net : Net {};
 
 // ============================================================================
 // C ABI
@@ -1380,9 +1626,9 @@ int f3_net_forward(f3_net* net, int N, int training, const float* params, float*
   F3_TRY(br.fork());
   // the skeleton streams' weight prep + data_bn first (the motion stream's queue waited ~130 us for
   // the host to submit the sensor branch ahead of it), then the sensor branch (small, latency-bound),
-  // then the skeleton streams stage by stage, interleaved, so every branch queue is fed early
+  // then the skeleton streams block by block, interleaved, so every branch queue is fed early
   for (int si = 0; si < net->nstreams; ++si)
-    F3_TRY(stream_forward(*net, si, N, training, q, w, w.skel, run, br.at(si), -1));
+    F3_TRY(stream_prep(*net, si, N, training, q, w, w.skel, run, br.at(si)));
   if (net->has_sensor) {
     const hipStream_t ss = br.at(2);
     LstmArgs la;
@@ -1404,9 +1650,8 @@ int f3_net_forward(f3_net* net, int N, int training, const float* params, float*
     F3_TRY(f3_shead_fwd(&sa, ss));
     if (training) add_bnrun(run, q, net->lstm.bn, w.sbn.fsum, w.sbn.fsq, N);
   }
-  for (int stage = 0; stage < 7; ++stage)
-    for (int si = 0; si < net->nstreams; ++si)
-      F3_TRY(stream_forward(*net, si, N, training, q, w, w.skel, run, br.at(si), stage));
+  for (int l = 0; l < 7; ++l)
+    for (int si = 0; si < net->nstreams; ++si) F3_TRY(layer_forward(*net, si, l, N, training, q, w, run, br.at(si)));
   F3_TRY(br.join());
   HeadArgs h;
   head_args(*net, N, q, w, h);
@@ -1445,91 +1690,6 @@ int f3_net_backward(f3_net* net, int N, const float* params, const float* dout, 
 }
 
 int64_t f3_net_grad_split(const f3_net* net) { return net ? net->nparam_phase1 : 0; }
-
-}  // extern "C"
-
-namespace {
-struct FusedOpt {
-  float *p, *sq;
-  float lr, alpha, eps;
-  const OptLaunch* gen = nullptr;  // f3_net_backward_optim
-};
-
-int net_backward(f3_net* net, int N, const float* params, const float* dout, float* grads, void* workspace, int phase,
-                 void* stream, const FusedOpt* opt);
-
-// the skeleton layers' ranges cover exactly their own parameter entries (the fused optimizer's
-// per-layer launches rely on it; checked once per call, ~300 entries)
-bool layer_ranges_ok(const f3_net& n) {
-  for (int si = 0; si < n.nstreams; ++si)
-    for (int l = 0; l < 7; ++l) {
-      const LayerIdx& L = n.st[si].L[l];
-      const RmsRanges r = layer_ranges(n, L);
-      long long sum = 0;
-      for (int i = L.gcn_w; i <= L.ca_b2; ++i) {
-        const Entry& e = n.entries[i];
-        if (e.kind != F3_ENTRY_PARAM) continue;
-        if (e.offset < r.lo[0] || e.offset >= r.lo[0] + r.len[0]) return false;
-        sum += (e.numel + 3) / 4 * 4;
-      }
-      if (sum != r.len[0]) return false;
-    }
-  return true;
-}
-
-// f3_net_backward_rmsprop's plan: whether the per-layer updates apply (a layout whose layer entries are
-// not contiguous cannot be updated per layer) and the leftover ranges updated after the join
-void fused_opt_plan(f3_net& n) {
-  n.fused_opt = layer_ranges_ok(n);
-  n.rest_ranges.clear();
-  n.rest_ranges_opt.clear();
-  // the no-gradient entries (whole padded entries, adjacent ones merged) for the flat update
-  n.nograd_skip.n = 0;
-  for (const Entry& e : n.entries) {
-    if (e.kind != F3_ENTRY_PARAM || !e.nograd) continue;
-    OptSkip& k = n.nograd_skip;
-    const long long lo = e.offset, len = (e.numel + 3) / 4 * 4;
-    if (k.n && k.lo[k.n - 1] + k.len[k.n - 1] == lo) k.len[k.n - 1] += len;
-    else if (k.n < kOptSkip) { k.lo[k.n] = lo; k.len[k.n] = len; ++k.n; }
-    else { n.nograd_skip.n = -1; break; }  // more ranges than the kernel takes: f3_net_backward_optim refuses
-  }
-  if (!n.fused_opt) return;
-  std::vector<std::pair<long long, long long>> done, rest, rest_opt;
-  for (int si = 0; si < n.nstreams; ++si)
-    for (int l = 0; l < 7; ++l) {
-      const RmsRanges r = layer_ranges(n, n.st[si].L[l]);
-      for (int j = 0; j < r.n; ++j) done.push_back({r.lo[j], r.lo[j] + r.len[j]});
-    }
-  for (const Entry& e : n.entries) {
-    if (e.kind != F3_ENTRY_PARAM) continue;
-    bool in = false;
-    for (auto& d : done) in = in || (e.offset >= d.first && e.offset < d.second);
-    if (in) continue;
-    const long long lo = e.offset, hi = e.offset + (e.numel + 3) / 4 * 4;
-    if (!rest.empty() && rest.back().second == lo) rest.back().second = hi;
-    else rest.push_back({lo, hi});
-    if (e.nograd) continue;
-    if (!rest_opt.empty() && rest_opt.back().second == lo) rest_opt.back().second = hi;
-    else rest_opt.push_back({lo, hi});
-  }
-  auto pack = [](const std::vector<std::pair<long long, long long>>& v, std::vector<RmsRanges>& out) {
-    RmsRanges r;
-    r.n = 0;
-    for (size_t i = 0; i < v.size(); ++i) {
-      r.lo[r.n] = v[i].first;
-      r.len[r.n] = v[i].second - v[i].first;
-      if (++r.n == kRmsRanges || i + 1 == v.size()) {
-        out.push_back(r);
-        r.n = 0;
-      }
-    }
-  };
-  pack(rest, n.rest_ranges);
-  pack(rest_opt, n.rest_ranges_opt);
-}
-}  // namespace
-
-extern "C" {
 
 int f3_net_backward_rmsprop(f3_net* net, int N, float* params, const float* dout, float* grads, float* square_avg,
                             void* workspace, float lr, float alpha, float eps, void* stream) {
@@ -1597,121 +1757,6 @@ int f3_net_backward_phase(f3_net* net, int N, const float* params, const float* 
   return net_backward(net, N, params, dout, grads, workspace, phase, stream, nullptr);
 }
 
-}  // extern "C"
-
-namespace {
-int net_backward(f3_net* net, int N, const float* params, const float* dout, float* grads, void* workspace, int phase,
-                 void* stream, const FusedOpt* opt) {
-  if (!net || !params || !grads || !workspace || N < 2 || phase < 0 || phase > 2) return F3_EINVAL;
-  if (phase != 2 && !dout) return F3_EINVAL;
-  F3_TRY(net->cstatus.take(false));
-  if (opt && phase != 0) return F3_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  Ws w = plan(*net, N, (char*)workspace);
-  Ptrs q{*net, params, nullptr, nullptr, grads};
-  if (opt) {
-    q.opt_p = opt->p; q.opt_sq = opt->sq; q.lr = opt->lr; q.alpha = opt->alpha; q.eps = opt->eps;
-    q.opt_gen = opt->gen;
-  }
-  // skeleton streams layer by layer, interleaved (see stream_forward)
-  // after_first: called once the first layer's main chains are submitted (the sensor backward, so its
-  // host submission does not hold back the skeleton streams' first layer)
-  auto skeleton = [&](Branches& br, int l_hi, int l_lo, const std::function<int()>& after_first) -> int {
-    // Each layer's main chains are submitted before the previous layer's side-stream work (the
-    // weight gradients): the host can be held up submitting to the long side queue, and the
-    // main queues should already hold their next layer by then (neutral in time since the side
-    // split, kept: it removed 150-490 us idle stretches of the main queues before it)
-    const bool defer = br.side() != br.s;
-    // Every layer's weight gradients run on the side queues. (A former F3_TAIL_SIDE=0 option ran
-    // layer 0's on the stream's own queue: measured neutral to 1 % slower, and it raced with the
-    // side queue's layer-1 launch on the stream's shared split-K slab, so it is gone.)
-    auto side_of = [&](int si, int) { return br.side(si); };
-    for (int l = l_hi; l >= l_lo; --l) {
-      for (int si = 0; si < net->nstreams; ++si) {
-        F3_TRY(stream_backward(*net, si, N, q, w, w.skel, br.at(si), l, l, side_of(si, l), l_hi,
-                               defer ? 1 : 3));
-        if (debug_stop(si, l)) return F3_OK;  // leave the scratch as is for f3_net_debug_tensor
-      }
-      if (l == l_hi && after_first) F3_TRY(after_first());
-      if (defer && l < l_hi)
-        for (int si = 0; si < net->nstreams; ++si)
-          F3_TRY(stream_backward(*net, si, N, q, w, w.skel, br.at(si), l + 1, l + 1, side_of(si, l + 1),
-                                 l_hi, 2));
-    }
-    if (defer)
-      for (int si = 0; si < net->nstreams; ++si)
-        F3_TRY(stream_backward(*net, si, N, q, w, w.skel, br.at(si), l_lo, l_lo, side_of(si, l_lo), l_hi, 2));
-    return F3_OK;
-  };
-  if (phase == 2) {
-    Branches br{*net, s, ensure_parallel(*net, s)};
-    // the same queue assignment as phase 1 (mask incl. the sensor queue, which carries the motion
-    // stream's weight gradients): a stream's split-K slab is then only ever used from one queue,
-    // so phase 2's weight gradients cannot overlap phase 1's still-draining ones on that slab
-    br.mask = (net->nstreams > 1 ? BR_MOTION : 0) | (net->has_sensor ? BR_SENSOR : 0) |
-              (net->nstreams > 0 ? BR_SIDE : 0);
-    F3_TRY(br.fork());
-    F3_TRY(skeleton(br, kSplitLayer - 1, 0, nullptr));
-    F3_TRY(br.join());
-    F3_TRY(wait_phase1(*net, s));  // phase 1's queues (e.g. the sensor queue) are done too
-    net->p1_mask = 0;
-    return F3_OK;
-  }
-  // the gradient buffer and the backward's zeroed workspace block: one launch when both are float
-  // ranges on 16-byte boundaries (the usual case), else two memsets
-  const size_t zb = w.zb1 - w.zb0;
-  if (zb % 4 == 0 && ((uintptr_t)grads | (uintptr_t)w.zb0) % 16 == 0) {
-    F3_TRY(f3_zero2(grads, net->nparam, reinterpret_cast<float*>(w.zb0), (long long)(zb / 4), s));
-  } else {
-    if (hipMemsetAsync(grads, 0, sizeof(float) * net->nparam, s) != hipSuccess) return F3_EHIP;
-    if (hipMemsetAsync(w.zb0, 0, zb, s) != hipSuccess) return F3_EHIP;
-  }
-  HeadArgs h;
-  head_args(*net, N, q, w, h);
-  h.g_out = dout;
-  LstmArgs la;
-  SHeadArgs sa;
-  Conv1dArgs c1, c2;
-  if (net->has_sensor) sensor_args(*net, N, 1, q, w, w.sensor, la, sa, c1, c2);
-  if (net->cfg.model == F3_MODEL_BILSTM) {
-    sa.dout = dout;
-    sa.dout_ld = net->cfg.num_class;
-  } else {
-    F3_TRY(f3_head_bwd_data(&h, s));  // dlogits + feature gradients: what the streams' backward waits for
-  }
-  Branches br{*net, s, ensure_parallel(*net, s)};
-  br.mask = (net->nstreams > 1 ? BR_MOTION : 0) | (net->has_sensor ? BR_SENSOR : 0) | (net->nstreams > 0 ? BR_SIDE : 0);
-  F3_TRY(br.fork());
-  // the head Linear's weight gradients off the critical path, at the front of the side queue (which
-  // then waits for the first layer's data gradients anyway)
-  if (net->cfg.model != F3_MODEL_BILSTM) F3_TRY(f3_head_bwd_weight(&h, br.side()));
-  auto sensor_bwd = [&]() -> int {
-    if (!net->has_sensor) return F3_OK;
-    const hipStream_t ss = br.at(2);
-    F3_TRY(f3_shead_bwd(&sa, ss));
-    F3_TRY(f3_lstm_bwd(&la, ss));
-    if (net->has_cnn) {
-      const CnnCoop coop{w.cpart, w.csyncb};
-      net->smark(2, ss);
-      F3_TRY(f3_cnn1d_bwd(&c1, &c2, &coop, ss));
-      net->smark(3, ss);
-      F3_TRY(net->cstatus.post(w.csyncb, ss));
-    }
-    return F3_OK;
-  };
-  // the skeleton streams' first layer is submitted before the sensor backward; a sensor-only model has
-  // no skeleton layer to wait for
-  if (net->nstreams == 0) F3_TRY(sensor_bwd());
-  F3_TRY(skeleton(br, 6, phase == 1 ? kSplitLayer : 0,
-                  net->nstreams == 0 ? std::function<int()>() : std::function<int()>(sensor_bwd)));
-  if (phase == 1) return br.mark_phase1();  // the caller orders its all-reduce after f3_net_wait_phase1
-  F3_TRY(br.join());
-  return F3_OK;
-}
-}  // namespace
-
-extern "C" {
-
 int f3_net_sensor_times(f3_net* net, int enable, float* ms) {
   if (!net) return F3_EINVAL;
   if (!net->has_cnn) return F3_EINVAL;
@@ -1741,370 +1786,6 @@ int f3_rmsprop_step(float* params, float* square_avg, const float* grads, int64_
                     float eps, float grad_scale, void* stream) {
   if (!params || !square_avg || !grads) return F3_EINVAL;
   return f3_rmsprop(params, square_avg, grads, n, lr, alpha, eps, grad_scale, (hipStream_t)stream);
-}
-
-// test-entry scratch (kept for the process lifetime; the network uses its workspace)
-static const unsigned short* test_zero_page() {
-  static void* z = nullptr;
-  if (!z && hipMalloc(&z, 4096) == hipSuccess) (void)hipMemset(z, 0, 4096);
-  return (const unsigned short*)z;
-}
-static float* test_scratch(size_t n) {
-  static float* p = nullptr;
-  static size_t cap = 0;
-  if (n > cap) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) return nullptr;
-    cap = n;
-  }
-  return p;
-}
-
-int f3_conv_forward(const void* x, const float* w, const float* bias, float* out, float* wpack, int N, int T_in,
-                    int V, int Cin, int Cout, int KT, int stride, int pad, int precision, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (precision < 0 || precision > F3_PRECISION_BF16X3) return F3_EINVAL;
-  const bool bf_out = precision == F3_CONV_BF16_OUT;
-  if (bf_out) precision = F3_PRECISION_BF16;
-  const int x3 = precision == F3_PRECISION_BF16X3;
-  const int hb = precision != F3_PRECISION_FP32;
-  if (w) {  // w == NULL: wpack already holds the packed operand (timing the GEMM alone)
-    PrepTable t;
-    t.n = 0;
-    add_job(t, PREP_PACK_CONV, Cout * KT * Cin, wpack, w, nullptr, nullptr, Cout, Cin, KT, x3 ? 2 : hb);
-    F3_TRY(f3_prep(t, s));
-  }
-  const int T_out = (T_in + 2 * pad - KT) / stride + 1;
-  ConvGemmArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.g = geom(N * T_out * V, Cout, Cin, KT, stride, pad, 0, T_out, T_in, V, Cin, Cout);
-  if (precision == F3_PRECISION_BF16) {
-    a.inb = (const unsigned short*)x;
-    a.zero = test_zero_page();
-  } else {
-    a.in = (const float*)x;
-  }
-  a.w = wpack; a.wb = bf(wpack, hb); a.out = out; a.bias = bias; a.x3 = x3;
-  if (bf_out) a.outb = reinterpret_cast<unsigned short*>(out);
-  return f3_conv_gemm(&a, 0, EPI_BIAS, s);
-}
-
-int f3_conv_backward_data(const void* dy, const float* w, float* dx, float* wpack, int N, int T_in, int V, int Cin,
-                          int Cout, int KT, int stride, int pad, int precision, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (precision < 0 || (precision > 2 && precision != F3_PRECISION_BF16X3)) return F3_EINVAL;
-  const int x3 = precision == F3_PRECISION_BF16X3;
-  const int hb = precision != F3_PRECISION_FP32;
-  PrepTable t;
-  t.n = 0;
-  add_job(t, PREP_PACK_CONV_T, Cout * KT * Cin, wpack, w, nullptr, nullptr, Cout, Cin, KT, x3 ? 2 : hb);
-  F3_TRY(f3_prep(t, s));
-  const int T_out = (T_in + 2 * pad - KT) / stride + 1;
-  ConvGemmArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.g = geom(N * T_in * V, Cin, Cout, KT, stride, pad, 1, T_in, T_out, V, Cout, Cin);
-  if (precision == F3_PRECISION_BF16) {
-    a.inb = (const unsigned short*)dy;
-    a.zero = test_zero_page();
-  } else {
-    a.in = (const float*)dy;
-  }
-  a.w = wpack; a.wb = bf(wpack, hb); a.out = dx; a.x3 = x3;
-  return f3_conv_gemm(&a, 0, 0, s);
-}
-
-int f3_pointwise_conv(const void* x, const void* wpack, const float* bias, void* out, int out_bf16, double* st_sum,
-                      double* st_sq, int N, int T_in, int T_out, int V, int Cin, int Cout, int stride, int transposed,
-                      int epi, void* stream) {
-  if (!x || !wpack || !out || N <= 0 || T_in <= 0 || T_out <= 0 || V <= 0 || (stride != 1 && stride != 2)) return F3_EINVAL;
-  if (epi != 0 && epi != EPI_BIAS && epi != (EPI_BIAS | EPI_STATS) && epi != (EPI_BIASV | EPI_STATS) && epi != EPI_ADD)
-    return F3_EINVAL;
-  if (transposed ? (T_in != (T_out - 1) / stride + 1) : (T_out != (T_in - 1) / stride + 1)) return F3_EINVAL;
-  if ((epi & EPI_ADD) && out_bf16) return F3_EINVAL;
-  if ((epi & EPI_STATS) && (!st_sum || !st_sq)) return F3_EINVAL;
-  if ((epi & (EPI_BIAS | EPI_BIASV)) && !bias) return F3_EINVAL;
-  ConvGemmArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.g = geom(N * T_out * V, Cout, Cin, 1, stride, 0, transposed, T_out, T_in, V, Cin, Cout);
-  a.inb = (const unsigned short*)x;
-  a.wb = (const unsigned short*)wpack;
-  a.zero = test_zero_page();
-  if (out_bf16) a.outb = (unsigned short*)out;
-  else a.out = (float*)out;
-  a.bias = bias; a.st_sum = st_sum; a.st_sq = st_sq;
-  if (!f3_igemm_ok(a)) return F3_EINVAL;
-  return f3_igemm_bf16(&a, epi, (hipStream_t)stream);
-}
-
-// ---- bf16x3 on the bf16 kernels, as the step launches them ([hi | lo] operand rows, native form) ----
-int f3_split_x3cat(const float* x, void* out, int64_t rows, int C, void* stream) {
-  if (!x || !out || rows < 0 || C <= 0 || C % 4) return F3_EINVAL;
-  return f3_split_x3(x, static_cast<unsigned short*>(out), rows, C, (hipStream_t)stream);
-}
-
-static bool x3cat_shape_ok(int N, int T_in, int V, int Cin, int Cout, int KT, int stride, int pad) {
-  return N > 0 && T_in > 0 && V > 0 && Cin > 0 && Cout > 0 && KT > 0 && (stride == 1 || stride == 2) && pad >= 0 &&
-         (T_in + 2 * pad - KT) / stride + 1 > 0 && Cin % 8 == 0 && Cout % 8 == 0;
-}
-
-int f3_conv_forward_x3cat(const void* x3, const float* w, const float* bias, float* out, void* wpack, int N, int T_in,
-                          int V, int Cin, int Cout, int KT, int stride, int pad, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!x3 || !bias || !out || !wpack || !x3cat_shape_ok(N, T_in, V, Cin, Cout, KT, stride, pad)) return F3_EINVAL;
-  if (w) {  // the step's packing (native [W_hi 32 | W_lo 32] blocks; w == NULL: wpack already packed)
-    PrepTable t;
-    t.n = 0;
-    add_job(t, PREP_PACK_CONV, Cout * KT * Cin * x3mul(x3code()), static_cast<float*>(wpack), w, nullptr, nullptr,
-            Cout, Cin, KT, x3code());
-    F3_TRY(f3_prep(t, s));
-  }
-  const int T_out = (T_in + 2 * pad - KT) / stride + 1;
-  ConvGemmArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.g = geom(N * T_out * V, Cout, Cin, KT, stride, pad, 0, T_out, T_in, V, 2 * Cin, Cout);
-  x3_gemm(a, Cin);
-  a.inb = static_cast<const unsigned short*>(x3); a.zero = test_zero_page();
-  a.wb = static_cast<const unsigned short*>(wpack); a.out = out; a.bias = bias;
-  if (!f3_igemm_ok(a)) return F3_EINVAL;
-  return f3_conv_gemm(&a, 0, EPI_BIAS, s);
-}
-
-int f3_conv_backward_data_x3cat(const void* dy3, const float* w, float* dx, void* wpack, int N, int T_in, int V,
-                                int Cin, int Cout, int KT, int stride, int pad, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!dy3 || !dx || !wpack || !x3cat_shape_ok(N, T_in, V, Cin, Cout, KT, stride, pad)) return F3_EINVAL;
-  if (w) {  // the transposed packing, as the step's
-    PrepTable t;
-    t.n = 0;
-    add_job(t, PREP_PACK_CONV_T, Cout * KT * Cin * x3mul(x3code()), static_cast<float*>(wpack), w, nullptr, nullptr,
-            Cout, Cin, KT, x3code());
-    F3_TRY(f3_prep(t, s));
-  }
-  const int T_out = (T_in + 2 * pad - KT) / stride + 1;
-  ConvGemmArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.g = geom(N * T_in * V, Cin, Cout, KT, stride, pad, 1, T_in, T_out, V, 2 * Cout, Cin);
-  x3_gemm(a, Cout);
-  a.inb = static_cast<const unsigned short*>(dy3); a.zero = test_zero_page();
-  a.wb = static_cast<const unsigned short*>(wpack); a.out = dx;
-  if (!f3_igemm_ok(a)) return F3_EINVAL;
-  return f3_conv_gemm(&a, 0, 0, s);
-}
-
-int f3_conv_step_x3cat(int kind, const void* in3, const float* w, void* wpack, float* out, const float* bias_v,
-                       const float* g, const float* gamma, const float* beta, const double* bn_sum,
-                       const double* bn_sq, float bn_count, double* st_sum, double* st_sq, int N, int T, int V,
-                       int Cin, int Cout, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const bool gcn = kind == F3_STEP_GCN_FWD, dgrad = kind == F3_STEP_TCN_DGRAD;
-  if ((!gcn && !dgrad) || !in3 || !wpack || !out || !st_sum || !st_sq) return F3_EINVAL;
-  if (gcn && !bias_v) return F3_EINVAL;
-  if (dgrad && (!g || !gamma || !beta || !bn_sum || !bn_sq || bn_count <= 0.f)) return F3_EINVAL;
-  const int KT = gcn ? 1 : 9, pad = gcn ? 0 : 4;
-  if (!x3cat_shape_ok(N, T, V, Cin, Cout, KT, 1, pad)) return F3_EINVAL;
-  if (w) {  // the step's packing (w == NULL: wpack already packed)
-    PrepTable t;
-    t.n = 0;
-    add_job(t, gcn ? PREP_PACK_CONV : PREP_PACK_CONV_T, Cout * KT * Cin * x3mul(x3code()), static_cast<float*>(wpack),
-            w, nullptr, nullptr, Cout, Cin, KT, x3code());
-    F3_TRY(f3_prep(t, s));
-  }
-  ConvGemmArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.inb = static_cast<const unsigned short*>(in3); a.zero = test_zero_page();
-  a.wb = static_cast<const unsigned short*>(wpack); a.out = out; a.st_sum = st_sum; a.st_sq = st_sq;
-  if (gcn) {  // stream_forward_layer's gcn GEMM: [Z_hi | Z_lo] rows of K Ci channels, graph-mixed bias, BN1 sums
-    a.g = geom(N * T * V, Cout, Cin, 1, 1, 0, 0, T, T, V, Cin, Cout);
-    x3_gemm(a, Cin);
-    a.bias = bias_v;
-    if (!f3_igemm_ok(a)) return F3_EINVAL;
-    return f3_conv_gemm(&a, 0, EPI_BIASV | EPI_STATS, s);
-  }
-  // stream_backward's tcn input gradient: dh rows [hi | lo] of Cout channels (the tcn's output) into
-  // dv[M][Cin]; ReLU mask of bn1(g) and the BN1-backward sums in the epilogue (RELUMASK)
-  a.g = geom(N * T * V, Cin, Cout, KT, 1, pad, 1, T, T, V, Cout, Cin);
-  x3_gemm(a, Cout);
-  a.aux = g; a.ldaux = Cin;
-  a.epi_bn.sum = bn_sum; a.epi_bn.sumsq = bn_sq; a.epi_bn.gamma = gamma; a.epi_bn.beta = beta;
-  a.epi_bn.count = bn_count; a.epi_bn.eval = 0;
-  if (!f3_igemm_ok(a)) return F3_EINVAL;
-  return f3_conv_gemm(&a, 0, EPI_RELUMASK, s);
-}
-
-int f3_conv_backward_weight_x3cat(const void* dy3, const void* x3, float* dw, float* db, int N, int T_in, int V,
-                                  int Cin, int Cout, int KT, int stride, int pad, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!dy3 || !x3 || !x3cat_shape_ok(N, T_in, V, Cin, Cout, KT, stride, pad)) return F3_EINVAL;
-  const int T_out = (T_in + 2 * pad - KT) / stride + 1;
-  const long long cap = kWgradSlabFloats * 4;  // the step's x3 slab (plan: W.slab)
-  float* slab = test_scratch((size_t)cap + 2 * Cout);
-  if (!slab) return F3_EHIP;
-  WgradArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.ldy = 2 * Cout; a.outmap = WG_OUT_CONV; a.bf16 = 1;
-  a.dyb = static_cast<const unsigned short*>(dy3); a.inb = static_cast<const unsigned short*>(x3);
-  a.zero = test_zero_page(); a.slab = slab; a.slab_cap = cap;
-  a.g = geom(N * T_out * V, Cout, Cin, KT, stride, pad, 0, T_out, T_in, V, 2 * Cin, Cout);
-  a.x3seg = 1;
-  if (dw) {  // dw == NULL: the GEMM alone (partials left in the slab)
-    if (hipMemsetAsync(dw, 0, sizeof(float) * Cout * Cin * KT, s) != hipSuccess) return F3_EHIP;
-    a.dw_ref = dw;
-    if (db) {
-      if (hipMemsetAsync(db, 0, sizeof(float) * Cout, s) != hipSuccess) return F3_EHIP;
-      a.db = db;
-    }
-  }
-  if (!f3_wgrad_glds_ok(a)) return F3_EINVAL;
-  return f3_conv_wgrad(&a, 0, s);
-}
-
-int f3_conv_backward_weight(const void* dy, const void* x, float* dw, float* db, int N, int T_in, int V, int Cin,
-                            int Cout, int KT, int stride, int pad, int precision, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (precision < 0 || (precision > 2 && precision != F3_PRECISION_BF16X3)) return F3_EINVAL;
-  const int T_out = (T_in + 2 * pad - KT) / stride + 1;
-  if (hipMemsetAsync(dw, 0, sizeof(float) * Cout * Cin * KT, s) != hipSuccess) return F3_EHIP;
-  if (db && hipMemsetAsync(db, 0, sizeof(float) * Cout, s) != hipSuccess) return F3_EHIP;
-  WgradArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.g = geom(N * T_out * V, Cout, Cin, KT, stride, pad, 0, T_out, T_in, V, Cin, Cout);
-  a.ldy = Cout; a.dw = dw; a.db = db; a.outmap = WG_OUT_CONV;
-  a.x3 = precision == F3_PRECISION_BF16X3;
-  a.bf16 = precision != F3_PRECISION_FP32 && !a.x3;
-  if (precision == F3_PRECISION_BF16) {
-    a.dyb = (const unsigned short*)dy;
-    a.inb = (const unsigned short*)x;
-    a.zero = test_zero_page();
-    if (f3_wgrad_glds_ok(a)) {  // split partials in a scratch slab, summed into dw (the step's path)
-      const long long cap = kWgradSlabFloats;
-      float* slab = test_scratch((size_t)cap);
-      if (!slab) return F3_EHIP;
-      a.slab = slab; a.slab_cap = cap; a.dw_ref = dw;
-      return f3_conv_wgrad(&a, 0, s);
-    }
-  } else {
-    a.dy = (const float*)dy;
-    a.in = (const float*)x;
-  }
-  return f3_conv_wgrad(&a, 0, s);
-}
-
-int f3_conv_wgrad_packed(const void* dy, const void* x, float* slab, long long slab_floats, int N, int T_in, int V,
-                         int Cin, int Cout, int KT, int stride, int pad, void* stream) {
-  if (!dy || !x || !slab || N < 1) return F3_EINVAL;
-  const int T_out = (T_in + 2 * pad - KT) / stride + 1;
-  WgradArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.g = geom(N * T_out * V, Cout, Cin, KT, stride, pad, 0, T_out, T_in, V, Cin, Cout);
-  a.ldy = Cout; a.dw = nullptr; a.db = nullptr; a.outmap = WG_OUT_CONV; a.bf16 = 1;
-  a.slab = slab; a.slab_cap = slab_floats; a.dw_ref = nullptr;  // the kernel alone: partials stay in the slab
-  a.dyb = (const unsigned short*)dy; a.inb = (const unsigned short*)x; a.zero = test_zero_page();
-  if (!f3_wgrad_glds_ok(a)) return F3_EINVAL;
-  return f3_conv_wgrad(&a, 0, (hipStream_t)stream);
-}
-
-int f3_graph_mix_forward(const float* A_eff, const float* x, float* z, int frames, int K, int V, int Cin,
-                         void* stream) {
-  MixArgs m;
-  std::memset(&m, 0, sizeof(m));
-  m.K = K; m.V = V; m.Cin = Cin; m.frames = frames; m.A = A_eff; m.x = x; m.z = z;
-  return f3_mix_fwd(&m, (hipStream_t)stream);
-}
-
-int f3_graph_mix_backward(const float* A_eff, const float* x, const float* dz, float* dx, float* dA, int frames, int K,
-                          int V, int Cin, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(dA, 0, sizeof(float) * K * V * V, s) != hipSuccess) return F3_EHIP;
-  MixArgs m;
-  std::memset(&m, 0, sizeof(m));
-  m.K = K; m.V = V; m.Cin = Cin; m.frames = frames; m.A = A_eff; m.x = x; m.z = const_cast<float*>(dz);
-  m.dx = dx; m.dA = dA; m.accumulate = 0;
-  static float* part = nullptr;  // test entry only: scratch kept for the process lifetime
-  if (!part && hipMalloc(&part, sizeof(float) * kMixParts * 1024) != hipSuccess) return F3_EHIP;
-  m.part = part;
-  return f3_mix_bwd(&m, s);
-}
-
-int f3_graph_mix_forward_ex(const float* A_eff, const void* x, void* z, int frames, int K, int V, int Cin, int flags,
-                            void* stream) {
-  if (!A_eff || !x || !z || frames < 0 || (flags & ~15) || ((flags & F3_MIX_X3) && (flags & 3))) return F3_EINVAL;
-  if ((flags & F3_MIX_Z3) && !(flags & F3_MIX_X3)) return F3_EINVAL;
-  MixArgs m;
-  std::memset(&m, 0, sizeof(m));
-  m.K = K; m.V = V; m.Cin = Cin; m.frames = frames; m.A = A_eff;
-  m.x = static_cast<const float*>(x); m.x16 = flags & F3_MIX_X_BF16; m.x3 = (flags & F3_MIX_X3) != 0;
-  m.z = static_cast<float*>(z);
-  if (flags & F3_MIX_Z_BF16) m.zb = static_cast<unsigned short*>(z);
-  if (flags & F3_MIX_Z3) m.z3 = static_cast<unsigned short*>(z);
-  return f3_mix_fwd(&m, (hipStream_t)stream);
-}
-
-int f3_graph_mix_backward_ex(const float* A_eff, const void* x, const void* dz, float* dx, float* dA, int frames, int K,
-                             int V, int Cin, int flags, void* stream) {
-  if (!A_eff || !x || !dz || !dx || !dA || frames < 0 || (flags & ~5) || ((flags & F3_MIX_X3) && (flags & 1)))
-    return F3_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  if (hipMemsetAsync(dA, 0, sizeof(float) * K * V * V, s) != hipSuccess) return F3_EHIP;
-  MixArgs m;
-  std::memset(&m, 0, sizeof(m));
-  m.K = K; m.V = V; m.Cin = Cin; m.frames = frames; m.A = A_eff; m.x = static_cast<const float*>(x);
-  m.dx = dx; m.dA = dA; m.accumulate = 0; m.x3 = (flags & F3_MIX_X3) != 0;
-  if (flags & F3_MIX_X_BF16) {
-    m.x16 = 1;
-    m.dzb = static_cast<const unsigned short*>(dz);
-  } else {
-    m.z = const_cast<float*>(static_cast<const float*>(dz));
-  }
-  static float* part = nullptr;  // test entry only: scratch kept for the process lifetime
-  if (!part && hipMalloc(&part, sizeof(float) * kMixParts * 1024) != hipSuccess) return F3_EHIP;
-  m.part = part;
-  return f3_mix_bwd(&m, s);
-}
-
-int f3_gcn_dgrad_mix_x3(const void* dg3, const float* w, void* wpack, const float* A_eff, const float* x, float* dx,
-                        float* dA, int frames, int K, int V, int Cin, int C, int accumulate, int max_workgroups,
-                        void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!dg3 || !wpack || !A_eff || !x || !dx || !dA || frames < 0 || max_workgroups < 0) return F3_EINVAL;
-  if (!f3_gcn_dgrad_mix_ok(K, V, Cin, C) || K * V * V > 1024) return F3_EINVAL;  // (the scratch rows below)
-  if (w) {  // the step's transposed packing of w [C][K Cin] (w == NULL: wpack already packed)
-    PrepTable t;
-    t.n = 0;
-    add_job(t, PREP_PACK_CONV_T, C * K * Cin * x3mul(x3code()), static_cast<float*>(wpack), w, nullptr, nullptr, C,
-            K * Cin, 1, x3code());
-    F3_TRY(f3_prep(t, s));
-  }
-  if (hipMemsetAsync(dA, 0, sizeof(float) * K * V * V, s) != hipSuccess) return F3_EHIP;
-  static float* part = nullptr;  // test entry only: scratch kept for the process lifetime
-  if (!part && hipMalloc(&part, sizeof(float) * kMixParts * 1024) != hipSuccess) return F3_EHIP;
-  GcnDgradMixArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.frames = frames; a.K = K; a.V = V; a.Cin = Cin; a.C = C; a.dg = static_cast<const unsigned short*>(dg3);
-  a.w = static_cast<const unsigned short*>(wpack); a.A = A_eff; a.x = x; a.dx = dx; a.dA = dA;
-  a.accumulate = accumulate != 0; a.part = part; a.max_workgroups = max_workgroups;
-  return f3_gcn_dgrad_mix(&a, s);
-}
-
-int f3_gcn_fwd_mix_x3(const float* A_eff, const float* x, const float* w, void* wpack, const float* bias_v, void* z3,
-                      float* g, double* st_sum, double* st_sq, int frames, int K, int V, int Cin, int C,
-                      void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!A_eff || !x || !wpack || !bias_v || !z3 || !g || !st_sum || !st_sq || frames < 0) return F3_EINVAL;
-  if (!f3_gcn_fwd_mix_ok(K, V, Cin, C)) return F3_EINVAL;
-  if (w) {  // the step's packing of w [C][K Cin] (w == NULL: wpack already packed)
-    PrepTable t;
-    t.n = 0;
-    add_job(t, PREP_PACK_CONV, C * K * Cin * x3mul(x3code()), static_cast<float*>(wpack), w, nullptr, nullptr, C,
-            K * Cin, 1, x3code());
-    F3_TRY(f3_prep(t, s));
-  }
-  GcnFwdMixArgs a;
-  std::memset(&a, 0, sizeof(a));
-  a.frames = frames; a.K = K; a.V = V; a.Cin = Cin; a.C = C; a.A = A_eff; a.x = x;
-  a.z3 = static_cast<unsigned short*>(z3); a.w = static_cast<const unsigned short*>(wpack); a.bias = bias_v; a.g = g;
-  a.st_sum = st_sum; a.st_sq = st_sq; a.zero = test_zero_page();
-  return f3_gcn_fwd_mix(&a, s);
 }
 
 // debug accessor (tests/tools only): device pointer of a named per-layer workspace tensor
