@@ -36,6 +36,7 @@ EXPORTS = (
     "f3_optim_scalars_bytes", "f3_optim_step", "f3_optim_step_ranges", "f3_net_backward_optim", "f3_net_entry_nograd",
     "f3_metrics_bytes", "f3_metrics_reset", "f3_metrics_update", "f3_segment_norms_scratch_bytes", "f3_segment_norms",
     "f3_soft_ce_ex", "f3_net_loss_ex", "f3_grad_accumulate",
+    "f3_optim_hyper_bytes", "f3_optim_hyper_set", "f3_optim_step_hyper",
 )
 
 F3_OK, F3_EINVAL, F3_EBATCH, F3_EHIP, F3_ESTATE, F3_EDEVICE = 0, 1001, 1002, 1003, 1004, 1005
@@ -108,6 +109,9 @@ def lib():
         "f3_optim_step": (I, [ctypes.POINTER(F3OptimConfig), P, P, P, P, I64, P, P]),
         "f3_optim_step_ranges": (I, [ctypes.POINTER(F3OptimConfig), P, P, P, P, I, ctypes.POINTER(I64),
                                      ctypes.POINTER(I64), P, P]),
+        "f3_optim_hyper_bytes": (I64, []),
+        "f3_optim_hyper_set": (I, [ctypes.POINTER(F3OptimConfig), P, P]),
+        "f3_optim_step_hyper": (I, [ctypes.POINTER(F3OptimConfig), P, P, P, P, I64, P, P, P]),
         "f3_net_backward_optim": (I, [P, I, P, P, P, P, P, P, P, ctypes.POINTER(F3OptimConfig), P]),
         "f3_net_entry_nograd": (I, [P, I]),
         "f3_metrics_bytes": (I64, [I]),

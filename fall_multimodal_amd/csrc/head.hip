@@ -249,6 +249,40 @@ __global__ void rmsprop_kernel(float* __restrict__ p, float* __restrict__ sq, co
   }
 }
 
+// rmsprop_kernel in the form a HIP graph records: the four values come from the hyper-parameter block when
+// the kernel runs, rounded to fp32 as f3_rmsprop_step's caller rounds them, so a replay follows the block.
+// Same bits as rmsprop_kernel on the same values (tests/test_gpu_optim_hyper.py), which takes some care:
+// that kernel leaves contraction to the compiler, and as built it fuses alpha * sv + t into one fma in the
+// float4 body and rounds the product and the sum separately in the scalar tail. Written again from the same
+// expressions, this kernel got the opposite choice in the tail (its operands sit in other registers), so it
+// turns contraction off and spells rmsprop_kernel's roundings out. rmsprop_kernel itself stays the code it
+// was: sharing one body through a device function already changes its instruction schedule.
+__global__ void rmsprop_hyper_kernel(float* __restrict__ p, float* __restrict__ sq, const float* __restrict__ g,
+                                     long long n, const OptHyper* __restrict__ h) {
+#pragma clang fp contract(off)
+  const float lr = (float)h->lr, alpha = (float)h->alpha, eps = (float)h->eps, scale = (float)h->grad_scale;
+  const long long n4 = n / 4;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n4; i += stride) {
+    f32x4 gv = reinterpret_cast<const f32x4*>(g)[i] * scale;
+    f32x4 sv = reinterpret_cast<f32x4*>(sq)[i];
+    f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      sv[e] = fmaf(alpha, sv[e], (1.f - alpha) * gv[e] * gv[e]);  // fused, as the float4 body of rmsprop_kernel
+      pv[e] -= lr * gv[e] / (sqrtf(sv[e]) + eps);
+    }
+    reinterpret_cast<f32x4*>(sq)[i] = sv;
+    reinterpret_cast<f32x4*>(p)[i] = pv;
+  }
+  for (long long i = n4 * 4 + blockIdx.x * (long long)blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float gv = g[i] * scale;
+    const float sv = alpha * sq[i] + (1.f - alpha) * gv * gv;  // two roundings, as its scalar tail
+    sq[i] = sv;
+    p[i] -= lr * gv / (sqrtf(sv) + eps);
+  }
+}
+
 __global__ void rmsprop_ranges_kernel(float* __restrict__ p, float* __restrict__ sq, const float* __restrict__ g,
                                       RmsRanges r, long long n4, float lr, float alpha, float eps, float scale) {
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -350,6 +384,15 @@ int f3_rmsprop(float* p, float* sq, const float* g, long long n, float lr, float
   const long long blocks = ((n / 4) + 255) / 256;
   const int grid = (int)(blocks < 4096 ? (blocks > 0 ? blocks : 1) : 4096);
   hipLaunchKernelGGL(rmsprop_kernel, dim3(grid), dim3(256), 0, s, p, sq, g, n, lr, alpha, eps, scale);
+  F3_LAUNCH_CHECK();
+  return F3_OK;
+}
+
+int f3_rmsprop_hyper(float* p, float* sq, const float* g, long long n, const OptHyper* h, hipStream_t s) {
+  if (n <= 0) return F3_OK;
+  const long long blocks = ((n / 4) + 255) / 256;
+  const int grid = (int)(blocks < 4096 ? (blocks > 0 ? blocks : 1) : 4096);
+  hipLaunchKernelGGL(rmsprop_hyper_kernel, dim3(grid), dim3(256), 0, s, p, sq, g, n, h);
   F3_LAUNCH_CHECK();
   return F3_OK;
 }

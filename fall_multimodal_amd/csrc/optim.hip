@@ -9,6 +9,10 @@
 // and rounded to fp32 once: m + (1-b1)(g - m) cancels, and an fp32 evaluation loses relative accuracy
 // of the result exactly there. The kernels are memory bound (3-4 loads, 2-3 stores per element), so
 // the fp64 VALU work is free. The one sqrt and the one division per element are fp32.
+//
+// The hyper-parameters reach the kernels by value (f3_optim_step), or, for a step recorded into a HIP
+// graph, from the OptHyper device block when the kernel runs (f3_optim_step_hyper, optim_hyper_kernel):
+// lr_scheduler.step(e) (model/main.py:321-322) then takes effect on a replay. Both forms give the same bits.
 #include <cmath>
 
 #include "common.h"
@@ -25,6 +29,19 @@ struct OptArgs {
   float lr_f, eps_f;
   int nesterov;
 };
+
+// The kernel arguments from the hyper-parameters as f3_optim_config carries them: evaluated on the host
+// for the by-value kernels and per thread in the device-reading ones (each is one IEEE operation or one
+// conversion, so both places give the same bits).
+__host__ __device__ inline OptArgs opt_args_of(double lr, double alpha, double eps, double mu, double b1, double b2,
+                                               double wd, double gscale, int nesterov) {
+#pragma clang fp contract(off)
+  OptArgs a;
+  a.lr = lr; a.a = alpha; a.oma = 1.0 - alpha; a.mu = mu;
+  a.b1 = b1; a.omb1 = 1.0 - b1; a.b2 = b2; a.omb2 = 1.0 - b2; a.wd = wd; a.gscale = gscale;
+  a.lr_f = (float)lr; a.eps_f = (float)eps; a.nesterov = nesterov;
+  return a;
+}
 
 // One element. contract(off): the flat and the ranges kernel, and the vector body and the scalar tail,
 // must round identically (the per-layer updates are compared bit for bit with the flat one).
@@ -109,6 +126,39 @@ __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, float
   }
 }
 
+// optim_kernel in the form a HIP graph records: every thread builds its OptArgs from the hyper-parameter
+// block once, before its loop, with opt_args_of's expressions (the ones the host evaluates for
+// optim_kernel), and the elements go through the same opt_update4 / opt_update, so the two forms give the
+// same bits on the same values and a replay follows the block. Which variant runs (KIND, nesterov) is the
+// step's structure and stays an argument. A kernel of its own with the loop written again: moving the
+// loop into a function shared with optim_kernel changes that kernel's instruction schedule, and the
+// by-value kernels are to stay the code they were.
+template <int KIND>
+__global__ __launch_bounds__(256) void optim_hyper_kernel(float* __restrict__ p, float* __restrict__ s0,
+                                                          float* __restrict__ s1, const float* __restrict__ g,
+                                                          long long n, const OptHyper* __restrict__ h, int nesterov,
+                                                          OptSkip skip, const OptScalars* __restrict__ sc) {
+  const OptArgs a = opt_args_of(h->lr, h->alpha, h->eps, h->momentum, h->beta1, h->beta2, h->weight_decay,
+                                h->grad_scale, nesterov);
+  const double sg = a.gscale * (double)sc->clip_coef;
+  const float bc1 = sc->bc1, bc2s = sc->bc2s;
+  const long long n4 = n / 4;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long t0 = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+  for (long long i = t0; i < n4; i += stride) {
+    if (skip.n && opt_skipped(skip, i * 4)) continue;
+    opt_update4<KIND>(p, s0, s1, g, i, a, sg, bc1, bc2s);
+  }
+  for (long long i = n4 * 4 + t0; i < n; i += stride) {
+    if (skip.n && opt_skipped(skip, i)) continue;
+    float pe = p[i], ae = KIND != OK_SGD0 ? s0[i] : 0.f, be = (KIND == OK_ADAM || KIND == OK_ADAMW) ? s1[i] : 0.f;
+    opt_update<KIND>(pe, ae, be, g[i], a, sg, bc1, bc2s);
+    p[i] = pe;
+    if (KIND != OK_SGD0) s0[i] = ae;
+    if (KIND == OK_ADAM || KIND == OK_ADAMW) s1[i] = be;
+  }
+}
+
 // ranges shape (as rmsprop_ranges_kernel): n4 float4s spread over r.n 16-byte-aligned ranges
 template <int KIND>
 __global__ __launch_bounds__(256) void optim_ranges_kernel(float* __restrict__ p, float* __restrict__ s0,
@@ -156,8 +206,8 @@ __global__ __launch_bounds__(256) void gradnorm_partials_kernel(const float* __r
 // once per optimizer step, one workgroup: t += 1, the bias corrections in fp64 from the integer t, the
 // norm from the partials in index order, the clip coefficient (clip_grad_norm_: max_norm / (norm + 1e-6),
 // clamped to 1; a non-finite norm propagates as in torch)
-__global__ void optim_begin_kernel(OptScalars* __restrict__ sc, int adam, double b1, double b2, double max_norm,
-                                   double gscale) {
+F3_DEV void optim_begin(OptScalars* __restrict__ sc, int adam, double b1, double b2, double max_norm,
+                        double gscale) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   const long long t = sc->t + 1;
   sc->t = t;
@@ -181,17 +231,33 @@ __global__ void optim_begin_kernel(OptScalars* __restrict__ sc, int adam, double
   sc->grad_norm = norm;
 }
 
+__global__ void optim_begin_kernel(OptScalars* __restrict__ sc, int adam, double b1, double b2, double max_norm,
+                                   double gscale) {
+  optim_begin(sc, adam, b1, b2, max_norm, gscale);
+}
+
+// The recorded form: the betas, max_norm and grad_scale from the block. Whether the step clips (the norm
+// partials were launched before this kernel) is structure: without it max_norm counts as 0.
+__global__ void optim_begin_hyper_kernel(OptScalars* __restrict__ sc, int adam, int clip,
+                                         const OptHyper* __restrict__ h) {
+  optim_begin(sc, adam, h->beta1, h->beta2, clip ? h->max_norm : 0.0, h->grad_scale);
+}
+
+// one thread: the nine values into the block (f3_optim_hyper_set), launched eagerly on the caller's stream
+__global__ void optim_hyper_write_kernel(OptHyper* __restrict__ h, OptHyper v) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  h->lr = v.lr; h->alpha = v.alpha; h->eps = v.eps; h->momentum = v.momentum;
+  h->beta1 = v.beta1; h->beta2 = v.beta2; h->weight_decay = v.weight_decay;
+  h->max_norm = v.max_norm; h->grad_scale = v.grad_scale;
+}
+
 }  // namespace f3
 
 using namespace f3;
 
 namespace {
 OptArgs opt_args(const OptLaunch& o) {
-  OptArgs a;
-  a.lr = o.lr; a.a = o.alpha; a.oma = 1.0 - o.alpha; a.mu = o.mu;
-  a.b1 = o.b1; a.omb1 = 1.0 - o.b1; a.b2 = o.b2; a.omb2 = 1.0 - o.b2; a.wd = o.wd; a.gscale = o.gscale;
-  a.lr_f = (float)o.lr; a.eps_f = (float)o.eps; a.nesterov = o.nesterov;
-  return a;
+  return opt_args_of(o.lr, o.alpha, o.eps, o.mu, o.b1, o.b2, o.wd, o.gscale, o.nesterov);
 }
 int opt_variant(const OptLaunch& o) { return o.kind == F3_OPT_SGD && o.mu == 0.0 ? (int)OK_SGD0 : o.kind; }
 int opt_grid(long long n4) {
@@ -199,28 +265,56 @@ int opt_grid(long long n4) {
   return (int)(blocks < 4096 ? (blocks > 0 ? blocks : 1) : 4096);
 }
 bool finite_nonneg(double v) { return std::isfinite(v) && v >= 0.0; }
+// the configuration's skip ranges for a flat update over n floats
+int opt_skip_of(const f3_optim_config* cfg, int64_t n, OptSkip* skip) {
+  if (n < 0 || cfg->nskip < 0 || cfg->nskip > F3_OPT_MAX_SKIP) return F3_EINVAL;
+  skip->n = cfg->nskip;
+  for (int j = 0; j < skip->n; ++j) {
+    skip->lo[j] = cfg->skip_lo[j];
+    skip->len[j] = cfg->skip_len[j];
+    if (skip->lo[j] < 0 || skip->len[j] < 0 || skip->lo[j] % 4 || skip->len[j] % 4 ||
+        skip->lo[j] + skip->len[j] > ((n + 3) / 4) * 4)
+      return F3_EINVAL;
+  }
+  return F3_OK;
+}
 }  // namespace
+
+// the kind and the values of a configuration, as every entry that takes one checks them
+static int opt_check_values(const f3_optim_config* c) {
+  if (!c || c->kind < F3_OPT_RMSPROP || c->kind > F3_OPT_ADAMW) return F3_EINVAL;
+  if (!finite_nonneg(c->lr) || !finite_nonneg(c->weight_decay) || !finite_nonneg(c->max_norm) ||
+      !std::isfinite(c->grad_scale) || c->grad_scale <= 0.0)
+    return F3_EINVAL;
+  if (c->kind == F3_OPT_RMSPROP) {
+    if (c->momentum != 0.0) return F3_EINVAL;  // RMSprop momentum: not built
+    if (!finite_nonneg(c->alpha) || c->alpha >= 1.0 || !finite_nonneg(c->eps)) return F3_EINVAL;
+  } else if (c->kind == F3_OPT_SGD) {
+    if (!finite_nonneg(c->momentum)) return F3_EINVAL;
+  } else {
+    if (!finite_nonneg(c->beta1) || c->beta1 >= 1.0 || !finite_nonneg(c->beta2) || c->beta2 >= 1.0 ||
+        !finite_nonneg(c->eps))
+      return F3_EINVAL;
+  }
+  return F3_OK;
+}
+
+// what the structure of a step (kind, momentum zero or not, nesterov) asks of the state pointers
+static int opt_check_states(const f3_optim_config* c, const float* s0, const float* s1) {
+  if (c->kind == F3_OPT_RMSPROP) return s0 ? F3_OK : F3_EINVAL;
+  if (c->kind == F3_OPT_SGD) {
+    if (c->nesterov && c->momentum == 0.0) return F3_EINVAL;  // torch: nesterov needs a momentum
+    return c->momentum != 0.0 && !s0 ? F3_EINVAL : F3_OK;
+  }
+  return s0 && s1 ? F3_OK : F3_EINVAL;
+}
 
 int f3_optim_resolve(const f3_optim_config* c, float* p, float* s0, float* s1, const float* g, void* scalars,
                      OptLaunch* o) {
   if (!c || !p || !g || !scalars || (uintptr_t)scalars % 8) return F3_EINVAL;
-  if (c->kind < F3_OPT_RMSPROP || c->kind > F3_OPT_ADAMW) return F3_EINVAL;
-  if (!finite_nonneg(c->lr) || !finite_nonneg(c->weight_decay) || !finite_nonneg(c->max_norm) ||
-      !std::isfinite(c->grad_scale) || c->grad_scale <= 0.0)
-    return F3_EINVAL;
+  F3_TRY(opt_check_values(c));
+  F3_TRY(opt_check_states(c, s0, s1));
   const bool adam = c->kind == F3_OPT_ADAM || c->kind == F3_OPT_ADAMW;
-  if (c->kind == F3_OPT_RMSPROP) {
-    if (c->momentum != 0.0) return F3_EINVAL;  // RMSprop momentum: not built
-    if (!finite_nonneg(c->alpha) || c->alpha >= 1.0 || !finite_nonneg(c->eps) || !s0) return F3_EINVAL;
-  } else if (c->kind == F3_OPT_SGD) {
-    if (!finite_nonneg(c->momentum)) return F3_EINVAL;
-    if (c->nesterov && c->momentum == 0.0) return F3_EINVAL;  // torch: nesterov needs a momentum
-    if (c->momentum != 0.0 && !s0) return F3_EINVAL;
-  } else {
-    if (!finite_nonneg(c->beta1) || c->beta1 >= 1.0 || !finite_nonneg(c->beta2) || c->beta2 >= 1.0 ||
-        !finite_nonneg(c->eps) || !s0 || !s1)
-      return F3_EINVAL;
-  }
   o->kind = c->kind; o->nesterov = c->nesterov != 0;
   o->lr = c->lr; o->alpha = c->alpha; o->eps = c->eps; o->mu = c->momentum;
   o->b1 = adam ? c->beta1 : 0.0; o->b2 = adam ? c->beta2 : 0.0;
@@ -241,8 +335,8 @@ int f3_optim_begin(const OptLaunch& o, long long n, hipStream_t s) {
   return F3_OK;
 }
 
-#define F3_OPT_DISPATCH(KERNEL, ...)                                                        \
-  switch (opt_variant(o)) {                                                                 \
+#define F3_OPT_DISPATCH(VARIANT, KERNEL, ...)                                               \
+  switch (VARIANT) {                                                                        \
     case OK_RMS: hipLaunchKernelGGL(KERNEL<OK_RMS>, __VA_ARGS__); break;                    \
     case OK_SGD: hipLaunchKernelGGL(KERNEL<OK_SGD>, __VA_ARGS__); break;                    \
     case OK_SGD0: hipLaunchKernelGGL(KERNEL<OK_SGD0>, __VA_ARGS__); break;                  \
@@ -260,7 +354,8 @@ int f3_optim_flat(const OptLaunch& o, long long n, const OptSkip& skip, hipStrea
     return f3_rmsprop(o.p, o.s0, o.g, n, (float)o.lr, (float)o.alpha, (float)o.eps, (float)o.gscale, s);
   const OptArgs a = opt_args(o);
   const OptScalars* sc = o.sc;
-  F3_OPT_DISPATCH(optim_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, o.p, o.s0, o.s1, o.g, n, a, skip, sc);
+  F3_OPT_DISPATCH(opt_variant(o), optim_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, o.p, o.s0, o.s1, o.g, n, a,
+                  skip, sc);
   F3_LAUNCH_CHECK();
   return F3_OK;
 }
@@ -279,7 +374,8 @@ int f3_optim_ranges(const OptLaunch& o, const RmsRanges& r, hipStream_t s) {
   if (n4 == 0) return F3_OK;
   const OptArgs a = opt_args(o);
   const OptScalars* sc = o.sc;
-  F3_OPT_DISPATCH(optim_ranges_kernel, dim3(opt_grid(n4)), dim3(256), 0, s, o.p, o.s0, o.s1, o.g, r, n4, a, sc);
+  F3_OPT_DISPATCH(opt_variant(o), optim_ranges_kernel, dim3(opt_grid(n4)), dim3(256), 0, s, o.p, o.s0, o.s1, o.g, r,
+                  n4, a, sc);
   F3_LAUNCH_CHECK();
   return F3_OK;
 }
@@ -292,19 +388,58 @@ int f3_optim_step(const f3_optim_config* cfg, float* params, float* state0, floa
                   int64_t n, void* scalars, void* stream) {
   OptLaunch o;
   F3_TRY(f3_optim_resolve(cfg, params, state0, state1, grads, scalars, &o));
-  if (n < 0 || cfg->nskip < 0 || cfg->nskip > F3_OPT_MAX_SKIP) return F3_EINVAL;
   OptSkip skip;
-  skip.n = cfg->nskip;
-  for (int j = 0; j < skip.n; ++j) {
-    skip.lo[j] = cfg->skip_lo[j];
-    skip.len[j] = cfg->skip_len[j];
-    if (skip.lo[j] < 0 || skip.len[j] < 0 || skip.lo[j] % 4 || skip.len[j] % 4 ||
-        skip.lo[j] + skip.len[j] > ((n + 3) / 4) * 4)
-      return F3_EINVAL;
-  }
+  F3_TRY(opt_skip_of(cfg, n, &skip));
   hipStream_t s = (hipStream_t)stream;
   F3_TRY(f3_optim_begin(o, n, s));
   return f3_optim_flat(o, n, skip, s);
+}
+
+int64_t f3_optim_hyper_bytes(void) { return (int64_t)sizeof(OptHyper); }
+
+int f3_optim_hyper_set(const f3_optim_config* cfg, void* hyper, void* stream) {
+  if (!hyper || (uintptr_t)hyper % 8) return F3_EINVAL;
+  F3_TRY(opt_check_values(cfg));
+  const OptHyper v = {cfg->lr, cfg->alpha, cfg->eps, cfg->momentum, cfg->beta1, cfg->beta2, cfg->weight_decay,
+                      cfg->max_norm, cfg->grad_scale};
+  hipLaunchKernelGGL(optim_hyper_write_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream,
+                     static_cast<OptHyper*>(hyper), v);
+  F3_LAUNCH_CHECK();
+  return F3_OK;
+}
+
+int f3_optim_step_hyper(const f3_optim_config* cfg, float* params, float* state0, float* state1, const float* grads,
+                        int64_t n, const void* hyper, void* scalars, void* stream) {
+  if (!cfg || !params || !grads || !hyper || (uintptr_t)hyper % 8) return F3_EINVAL;
+  if (cfg->kind < F3_OPT_RMSPROP || cfg->kind > F3_OPT_ADAMW) return F3_EINVAL;
+  if (cfg->kind == F3_OPT_RMSPROP && cfg->momentum != 0.0) return F3_EINVAL;  // RMSprop momentum: not built
+  F3_TRY(opt_check_states(cfg, state0, state1));
+  OptSkip skip;
+  F3_TRY(opt_skip_of(cfg, n, &skip));
+  if (((uintptr_t)params | (uintptr_t)state0 | (uintptr_t)state1 | (uintptr_t)grads) % 16) return F3_EINVAL;
+  const OptHyper* h = static_cast<const OptHyper*>(hyper);
+  hipStream_t s = (hipStream_t)stream;
+  // the structure, from cfg: the plain-RMSprop route, clipping on or off, the kernel variant
+  const bool clip = cfg->max_norm > 0.0;
+  if (cfg->kind == F3_OPT_RMSPROP && cfg->weight_decay == 0.0 && !clip)
+    return f3_rmsprop_hyper(params, state0, grads, n, h, s);  // skipped entries: as in f3_optim_flat
+  if (!scalars || (uintptr_t)scalars % 8) return F3_EINVAL;
+  OptScalars* sc = static_cast<OptScalars*>(scalars);
+  if (clip) {
+    hipLaunchKernelGGL(gradnorm_partials_kernel, dim3(kNormBlocks), dim3(256), 0, s, grads, n, sc->partials);
+    F3_LAUNCH_CHECK();
+  }
+  const int adam = cfg->kind == F3_OPT_ADAM || cfg->kind == F3_OPT_ADAMW;
+  hipLaunchKernelGGL(optim_begin_hyper_kernel, dim3(1), dim3(64), 0, s, sc, adam, (int)clip, h);
+  F3_LAUNCH_CHECK();
+  if (n == 0) return F3_OK;
+  const int variant = cfg->kind == F3_OPT_SGD && cfg->momentum == 0.0 ? (int)OK_SGD0 : cfg->kind;
+  const int nesterov = cfg->nesterov != 0;
+  const OptScalars* csc = sc;
+  F3_OPT_DISPATCH(variant, optim_hyper_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, params, state0, state1, grads,
+                  (long long)n, h, nesterov, skip, csc);
+  F3_LAUNCH_CHECK();
+  return F3_OK;
 }
 
 int f3_optim_step_ranges(const f3_optim_config* cfg, float* params, float* state0, float* state1,

@@ -141,6 +141,13 @@ int f3_rmsprop_ranges(float* p, float* sq, const float* g, const RmsRanges& r, f
                       float scale, hipStream_t s);
 int f3_rmsprop(float* p, float* sq, const float* g, long long n, float lr, float alpha, float eps, float scale,
                hipStream_t s);
+// The device block behind f3_optim_hyper_bytes(): f3_optim_config's values as the host passes them, read
+// by the update launches a HIP graph records (f3_optim_step_hyper), so a replay follows a scheduler.
+struct OptHyper {
+  double lr, alpha, eps, momentum, beta1, beta2, weight_decay, max_norm, grad_scale;
+};
+// f3_rmsprop with (float) lr, alpha, eps, grad_scale read from the block inside the kernel
+int f3_rmsprop_hyper(float* p, float* sq, const float* g, long long n, const OptHyper* h, hipStream_t s);
 
 // SGD / Adam / AdamW / RMSprop-with-decay updates (optim.hip; arithmetic in include/fall3.h).
 constexpr int kNormBlocks = 256;  // the grad-norm reduction's fixed grid: one fp64 partial per workgroup

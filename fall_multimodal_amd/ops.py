@@ -351,6 +351,20 @@ def scalar_views(scalars: Tensor):
     return (scalars[0:2].view(torch.int64), scalars[2:3], scalars[3:4], scalars[4:5], scalars[5:6])
 
 
+HYPER_FIELDS = ("lr", "alpha", "eps", "momentum", "beta1", "beta2", "weight_decay", "max_norm", "grad_scale")
+
+
+def optim_hyper(device):
+    """A zeroed hyper-parameter block (f3_optim_hyper_bytes) as an fp64 tensor; f3_optim_hyper_set writes
+    it, the update launches of f3_optim_step_hyper read it."""
+    return torch.zeros(int(lib().f3_optim_hyper_bytes()) // 8, dtype=torch.float64, device=device)
+
+
+def hyper_views(block: Tensor):
+    """The block's values as a float64 view, in HYPER_FIELDS order (the layout include/fall3.h documents)."""
+    return block.view(torch.float64)[:len(HYPER_FIELDS)]
+
+
 @torch.library.custom_op("fall3::optim_", mutates_args=("param", "state0", "state1", "scalars"))
 def optim_(param: Tensor, state0: Tensor, state1: Tensor, scalars: Tensor, grad: Tensor, kind: int, nesterov: bool,
            lr: float, alpha: float, eps: float, momentum: float, beta1: float, beta2: float, weight_decay: float,

@@ -80,6 +80,21 @@ def hyper(kind, group):
                 beta2=float(b[1]), weight_decay=float(group.get("weight_decay", 0.0)))
 
 
+STRUCTURE_FIELDS = ("the optimizer kind", "nesterov", "momentum zero / nonzero",
+                    "plain RMSprop (no weight decay, no clipping) or not", "max_norm off / on")
+
+
+def hyper_structure(kind, group, max_norm):
+    """What a recorded optimizer graph fixes: which launches the step has and which kernel variant they
+    run, (kind, nesterov, momentum != 0, legacy, max_norm > 0) in STRUCTURE_FIELDS order. legacy is plain
+    RMSprop, f3_rmsprop_step's kernel. Everything else of a param_group and of max_norm is a value: the
+    device block of f3_optim_hyper_set carries it and a replayed graph follows it."""
+    h = hyper(kind, group)
+    clip = bool(max_norm) and max_norm > 0
+    legacy = kind == "rmsprop" and h["weight_decay"] == 0 and not max_norm
+    return (kind, h["nesterov"] if kind == "sgd" else False, h["momentum"] != 0, legacy, clip)
+
+
 def torch_defaults(kind, **over):
     """A complete param_group (without 'params') as torch.optim.<kind> builds it, so a state_dict's
     param_groups carries every key torch's own would."""

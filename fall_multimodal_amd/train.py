@@ -124,7 +124,12 @@ def step_kwargs(config):
 class TrainStep:
     """`optimizer` (optional, e.g. fall3 RMSprop driven by a CosineLRScheduler): its
     param_groups[0] lr / alpha / eps are read at every step, so a scheduler's step(epoch) takes
-    effect as with the reference's optimizer.step() (model/main.py:127, 321-322).
+    effect as with the reference's optimizer.step() (model/main.py:127, 321-322). A captured step
+    follows them too: its optimizer graph reads lr, alpha, eps, momentum, betas, weight_decay, max_norm and
+    1/world from a device block (`hyper`; ops.hyper_views) that every call rewrites when one of them has
+    changed, with one small launch before the replay and none otherwise. What the graph fixes is the
+    step's structure (optim.hyper_structure: the kind, nesterov, momentum zero or not, plain RMSprop or
+    not, clipping on or off); a call after one of those changed raises ValueError: capture() again.
 
     The optimizer's class picks the update: f3.RMSprop / SGD / Adam / AdamW (or torch.optim's), with the
     hyper-parameters of its param_groups[0] (momentum, nesterov, betas, weight_decay, ...), also read at
@@ -187,6 +192,10 @@ class TrainStep:
         self.step_count, _, _, self.clip_coef, self.grad_norm = ops.scalar_views(self.scalars)
         self._legacy_steps = 0  # steps of the plain-RMSprop launches (which keep no device count)
         self._graph_legacy = False
+        # a captured step's hyper-parameter block (f3_optim_hyper_bytes), the structure its optimizer graph
+        # was recorded for and the values last written to the block; capture() sets all three
+        self.hyper = None
+        self._hyper_key = self._hyper_values = None
         # the entries no backward writes (f3_net_entry_nograd): skipped by every non-RMSprop update
         h0 = nat.h
         self._nograd = {name for i, (name, kind, _, _) in enumerate(nat.entries)
@@ -339,6 +348,38 @@ class TrainStep:
         if self.accum is not None:
             self._accum_reset.fill_(1)
 
+    # -- the captured update: structure fixed when recorded, values from the device block ---------
+    def _hyper_now(self):
+        """(structure key, the values in ops.HYPER_FIELDS order) of the group, max_norm and 1/world in force."""
+        g = self._group()
+        if self.optimizer is not None:
+            self.lr, self.alpha, self.eps = g["lr"], g.get("alpha", self.alpha), g.get("eps", self.eps)
+        _optim.check_supported(self.kind, g)
+        h = _optim.hyper(self.kind, g)
+        if self._legacy(g):  # the three values the eager plain-RMSprop launch passes
+            h.update(lr=float(self.lr), alpha=float(self.alpha), eps=float(self.eps))
+        h.update(max_norm=float(self.max_norm or 0.0), grad_scale=1.0 / self.world)
+        return _optim.hyper_structure(self.kind, g, self.max_norm), tuple(h[k] for k in ops.HYPER_FIELDS)
+
+    def _hyper_write(self, values):
+        """One eager launch on the current stream (f3_optim_hyper_set), ordered before the next replay."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TrainStep: the hyper-parameter block is written eagerly, never inside a capture")
+        cfg = ops.optim_config(kind=_optim.KIND_IDS[self.kind], nesterov=False, **dict(zip(ops.HYPER_FIELDS, values)))
+        check(lib().f3_optim_hyper_set(cfg, ptr(self.hyper), stream_handle()), f"{self.kind} hyper-parameters")
+        self._hyper_values = values
+
+    def _hyper_sync(self):
+        """Before a replay of the optimizer graph: a changed structure raises (the graph holds other
+        launches), changed values are written to the block, and nothing changed issues no launch."""
+        key, values = self._hyper_now()
+        if key != self._hyper_key:
+            changed = [name for name, a, b in zip(_optim.STRUCTURE_FIELDS, self._hyper_key, key) if a != b]
+            raise ValueError(f"TrainStep: {', '.join(changed)} changed since capture() ({self._hyper_key} -> {key}): "
+                             "the captured optimizer graph runs other launches, capture the step again")
+        if values != self._hyper_values:
+            self._hyper_write(values)
+
     # -- accumulation (accum_iter > 1) ----------------------------------------------
     def _need_accum(self, what):
         if self.accum is None:
@@ -412,6 +453,8 @@ class TrainStep:
     def _accum_call(self, skel, sensor, label, update):
         """One micro-batch of an accumulating step; the all-reduce and the update on update calls only."""
         do_update = self._update_due(update)
+        if do_update and self.graph is not None:
+            self._hyper_sync()  # raises before anything runs; a write is ordered before the replay below
         if self.graph is None:
             self.forward_backward(skel, sensor, label)
             self.accumulate()
@@ -450,6 +493,7 @@ class TrainStep:
         if self.graph is None:
             self._eager(skel, sensor, label)
             return self.loss
+        self._hyper_sync()  # raises before anything runs; a write is ordered before g_opt's replay
         self._load_static(skel, sensor, label)
         g_head, g_tail, g_opt = self.graph
         if self._graph_legacy:
@@ -471,7 +515,9 @@ class TrainStep:
         world > 1: [fwd+loss+bwd phase 1], [bwd phase 2], [RMSprop], with the two all-reduce
         buckets issued between replays. accum_iter > 1: [fwd+loss+bwd+accumulate], [update on
         accum, set the reset word]; the second is replayed on update calls only, after the all-reduce
-        of accum at world > 1. A pending accumulation is kept."""
+        of accum at world > 1. A pending accumulation is kept. The optimizer graph holds
+        f3_optim_step_hyper: the hyper-parameters in force are written to the device block here and
+        whenever they have changed before a replay, so the captured step follows a scheduler."""
         self._static = (skel, sensor, label)
         kept = self.metrics.snapshot() if self.metrics is not None else None  # the warm-up steps must not count
         side = torch.cuda.Stream()
@@ -501,9 +547,22 @@ class TrainStep:
         else:
             with torch.cuda.graph(g_head):
                 self.forward_backward(skel, sensor, label)
+        # the update in its device-reading form (f3_optim_step_hyper): the graph fixes which launches run
+        # (the structure key), the block written here and before later replays (_hyper_sync) gives the values
+        key, values = self._hyper_now()
+        cfg, s0, s1 = self._config(self._group(), 1.0 / self.world)
+        if self.hyper is None:
+            self.hyper = ops.optim_hyper(self.grads.device)
+        self._hyper_write(values)
+        src = self._gsrc
         g_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g_opt):
-            self.optimizer_step()
+            check(lib().f3_optim_step_hyper(cfg, ptr(self.model.flat_parameters()), ptr(s0), ptr(s1), ptr(src),
+                                            src.numel(), ptr(self.hyper), ptr(self.scalars), stream_handle()),
+                  f"{self.kind} step")
+            if self.accum is not None:
+                self._accum_reset.fill_(1)
+        self._hyper_key = key
         self._graph_legacy = self._legacy(self._group())
         self.graph = (g_head, g_tail, g_opt)
 
@@ -548,7 +607,7 @@ class TrainStep:
     def load_optimizer_state_dict(self, sd):
         """Restore the flat states, the step count and the hyper-parameters from a state_dict written by
         optimizer_state_dict() or by torch.optim.<kind>(model.parameters()) (in place: a captured graph stays valid,
-        but keeps the hyper-parameters it baked in)."""
+        and its next replay runs with the loaded hyper-parameters)."""
         bufs, step, group = _optim.state_dict_to_flat(self.kind, sd, self._layout(), self.grads.numel(),
                                                       device=self.grads.device)
         keys = _optim.state_keys(self.kind, group)

@@ -15,6 +15,8 @@
  *   f3_optim_step      <- clip_grad_norm_(); optimizer.step() for torch.optim.SGD / Adam / AdamW /
  *                         RMSprop with weight decay   model/optimizer.py:20-29, root main.py:108-113
  *   f3_net_backward_optim <- loss.backward(); clip_grad_norm_(); optimizer.step() in one call
+ *   f3_optim_hyper_set <- lr_scheduler.step(e)           model/main.py:321-322 (for a step recorded in a graph)
+ *   f3_optim_step_hyper <- optimizer.step()              model/main.py:127, hyper-parameters read on the device
  *   f3_metrics_update  <- cal_top_k_accuracy(), running loss, confusion matrix   model/main.py:57-77,
  *                         134-135, 189-200 (accumulated on the device: no copy or sync per batch)
  *   f3_segment_norms   <- param.grad.norm().item() per parameter   model/main.py:84-89
@@ -207,6 +209,34 @@ int f3_optim_step(const f3_optim_config* cfg, float* params, float* state0, floa
 int f3_optim_step_ranges(const f3_optim_config* cfg, float* params, float* state0, float* state1,
                          const float* grads, int nranges, const int64_t* lo, const int64_t* len, void* scalars,
                          void* stream);
+/* ---- the hyper-parameters as device values: an update recorded into a HIP graph follows a scheduler ----
+ * f3_optim_step and f3_rmsprop_step take lr, betas, ... by value, so a graph that recorded them replays
+ * the values it was recorded with. The hyper block is device memory of f3_optim_hyper_bytes() bytes
+ * (72), 8-byte aligned, holding the fp64 values of f3_optim_config as the host passes them:
+ *   byte 0 lr, 8 alpha, 16 eps, 24 momentum, 32 beta1, 40 beta2, 48 weight_decay, 56 max_norm,
+ *   64 grad_scale.
+ * The update launches of f3_optim_step_hyper read it when they run and derive their arguments with the
+ * expressions f3_optim_step evaluates on the host, so both forms give the same bits on the same values.
+ * What a recorded step cannot take from the block is its structure, which launches run and which kernel
+ * variant: the kind, momentum zero or not, nesterov, max_norm zero or not, and RMSprop with weight_decay
+ * 0 and max_norm 0 (f3_rmsprop_step's kernel). The configuration argument supplies those. */
+int64_t f3_optim_hyper_bytes(void);
+/* lr_scheduler.step(e) (model/main.py:321-322), or any other change of param_groups[0] / TRAIN.MAX_NORM /
+ * the world size, made visible to the recorded update: checks cfg's kind and values as f3_optim_step
+ * does (finite, non-negative, alpha / betas < 1, grad_scale > 0, no RMSprop momentum), then one
+ * one-thread launch on `stream` stores the nine values into the block. To be called outside stream
+ * capture, ordered before the replay on the same stream. F3_EINVAL (nothing launched, the block as it
+ * was): a bad value, hyper NULL or not 8-byte aligned. cfg's nesterov and skip ranges are not read. */
+int f3_optim_hyper_set(const f3_optim_config* cfg, void* hyper, void* stream);
+/* optimizer.step() (model/main.py:127) preceded by clip_grad_norm_ (root main.py:108-113), as
+ * f3_optim_step issues them: [norm partials], begin, one flat update over n floats, each in the form that
+ * reads its values from `hyper`. From cfg only the structure (above) and the skip ranges are taken; its
+ * lr, alpha, eps, betas, weight_decay, grad_scale and the magnitudes of momentum and max_norm are ignored.
+ * RMSprop with weight_decay 0 and max_norm 0 in cfg is f3_rmsprop_step's kernel reading (float) lr,
+ * alpha, eps, grad_scale from the block: as that call it touches no scalars (scalars may be NULL) and
+ * keeps no step count. Same bits as f3_optim_step / f3_rmsprop_step given the block's values. */
+int f3_optim_step_hyper(const f3_optim_config* cfg, float* params, float* state0, float* state1, const float* grads,
+                        int64_t n, const void* hyper, void* scalars, void* stream);
 /* loss.backward(); [clip_grad_norm_;] optimizer.step() (model/main.py:115-127) in one call: the
  * generalisation of f3_net_backward_rmsprop. Without clipping the begin kernel runs before the
  * private queues fork and each skeleton layer's update is issued on the queue that finishes its
