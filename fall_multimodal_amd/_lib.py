@@ -22,7 +22,7 @@ EXPORTS = (
     "f3_net_debug_tensor", "f3_conv_backward_data", "f3_conv_backward_weight", "f3_conv_wgrad_packed", "f3_split_x3cat",
     "f3_conv_forward_x3cat", "f3_conv_backward_data_x3cat", "f3_conv_backward_weight_x3cat", "f3_conv_step_x3cat", "f3_graph_mix_forward",
     "f3_graph_mix_backward", "f3_graph_mix_forward_ex", "f3_graph_mix_backward_ex", "f3_gcn_dgrad_mix_x3",
-    "f3_gcn_fwd_mix_x3",
+    "f3_gcn_fwd_mix_x3", "f3_block_signs_case",
     "f3_net_backward_phase",
     "f3_net_grad_split", "f3_net_wait_phase1", "f3_net_backward_rmsprop", "f3_net_fused_rmsprop", "f3_net_precision", "f3_net_status",
     "f3_targcn_create", "f3_targcn_destroy", "f3_targcn_num_entries", "f3_targcn_entry", "f3_targcn_param_count",
@@ -139,6 +139,7 @@ def lib():
         "f3_graph_mix_backward_ex": (I, [P, P, P, P, P, I, I, I, I, I, P]),
         "f3_gcn_dgrad_mix_x3": (I, [P, P, P, P, P, P, P, I, I, I, I, I, I, I, P]),
         "f3_gcn_fwd_mix_x3": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, P]),
+        "f3_block_signs_case": (I, [I] + [P] * 13 + [ctypes.c_longlong] + [P] * 5 + [I] * 6 + [P]),
         "f3_targcn_create": (I, [ctypes.POINTER(F3TargcnConfig), ctypes.POINTER(P)]),
         "f3_targcn_destroy": (None, [P]),
         "f3_targcn_num_entries": (I, [P]),

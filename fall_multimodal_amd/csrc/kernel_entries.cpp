@@ -379,4 +379,50 @@ int f3_gcn_fwd_mix_x3(const float* A_eff, const float* x, const float* w, void* 
   return f3_gcn_fwd_mix(&a, s);
 }
 
+int f3_block_signs_case(int phases, const void* h, const void* r, const void* x, const float* att, const float* e,
+                        const float* bn2, const float* bnr, const double* bn2_b, const double* bnr_b,
+                        const float* dout, const float* dout_nc, void* out, void* signs, long long sign_words,
+                        float* part, void* dh, void* dres, float* dbpart, float* dgb, int N, int TV, int C,
+                        int res_kind, int act16, int x3, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (N <= 0 || TV <= 0 || C < 4 || C % 4 || C > 256 || 256 % (C / 4)) return F3_EINVAL;
+  if (res_kind < RES_NONE || res_kind > RES_CONV || (act16 && x3)) return F3_EINVAL;
+  if (!h || !att || !bn2 || !out || (res_kind == RES_CONV && (!r || !bnr)) || (res_kind == RES_ID && !x)) return F3_EINVAL;
+  if (signs && sign_words < f3_block_sign_words(N, TV, C)) return F3_EINVAL;
+  BlockArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.N = N; a.TV = TV; a.C = C; a.res_kind = res_kind; a.inv_tv = 1.f / (float)TV; a.act16 = act16;
+  // BN rows [gamma | beta | mean | var] of C: the running-statistics form, so the caller owns every input
+  a.bn2.gamma = bn2; a.bn2.beta = bn2 + C; a.bn2.rmean = bn2 + 2 * C; a.bn2.rvar = bn2 + 3 * C;
+  a.bn2.count = (float)N * (float)TV; a.bn2.eval = 1;
+  if (res_kind == RES_CONV) {
+    a.bnr = a.bn2;
+    a.bnr.gamma = bnr; a.bnr.beta = bnr + C; a.bnr.rmean = bnr + 2 * C; a.bnr.rvar = bnr + 3 * C;
+  }
+  a.h = static_cast<const float*>(h); a.r = static_cast<const float*>(r); a.x = static_cast<const float*>(x);
+  a.att = att; a.out = static_cast<float*>(out); a.signs = static_cast<unsigned short*>(signs);
+  if (phases & 1) F3_TRY(f3_block_out(a, s));
+  if (!(phases & 2)) return F3_OK;
+  if (!e || !bn2_b || !part || !dh || !dgb || (!dout && !dout_nc) || (res_kind == RES_CONV && !bnr_b) ||
+      (res_kind != RES_NONE && !dres))
+    return F3_EINVAL;
+  a.dout = dout_nc ? nullptr : dout; a.dout_nc = dout_nc; a.e = e;
+  a.bn2_bsum = bn2_b; a.bn2_bsq = bn2_b + C;
+  if (res_kind == RES_CONV) {
+    a.bnr_bsum = const_cast<double*>(bnr_b); a.bnr_bsq = const_cast<double*>(bnr_b) + C;  // (read only here)
+  }
+  a.dgamma2 = dgb; a.dbeta2 = dgb + C; a.dgammar = dgb + 2 * C; a.dbetar = dgb + 3 * C;
+  a.part = part; a.no_colsum = 1;  // the P1 / P2 / Q2 partial rows stay in part [chunks][3][N][C]
+  a.dh = static_cast<float*>(dh);
+  a.dres = static_cast<float*>(dres);
+  const bool gemm_rows = act16 || x3;  // dh / dres as the step's GEMM operands: bf16, or [hi | lo] rows
+  a.dhb = gemm_rows ? static_cast<unsigned short*>(dh) : nullptr;
+  a.dresb = gemm_rows && res_kind == RES_CONV ? static_cast<unsigned short*>(dres) : nullptr;
+  a.x3 = x3;
+  F3_TRY(f3_block_bwd_reduce(a, s));
+  a.no_colsum = 0;
+  a.dbpart = dbpart;
+  return f3_block_bwd_apply(a, s);
+}
+
 }  // extern "C"

@@ -159,6 +159,10 @@ struct BlockArgs {
   // weight-gradient kernels then run without their in-loop bias sums. null: not written
   float* dbpart;
   int no_colsum;  // block_bwd_reduce: leave P1 / P2 / Q2 in `part` (ca_bwd1x sums them, CaArgs::bpart)
+  // ReLU sign words (f3_block_sign_words of them): block_out writes bit 4u+e of word
+  // [(n * chunks + chunk) * trips + trip][tid] = (stored out > 0) for row u, channel e of thread tid's
+  // trip; block_bwd_reduce / block_bwd_apply then read the words and never `out`. null: they read `out`
+  unsigned short* signs;
 };
 
 struct BnBwdArgs {
@@ -280,6 +284,7 @@ int f3_block_bwd_reduce(f3::BlockArgs a, hipStream_t s);
 int f3_block_bwd_apply(f3::BlockArgs a, hipStream_t s);
 int f3_bn_bwd_apply(f3::BnBwdArgs a, hipStream_t s);
 int f3_bn_bwd_parts(int N, int TV, int V);  // Gpart rows f3_bn_bwd_apply writes
+long long f3_block_sign_words(int N, int TV, int C);  // uint16 words of BlockArgs::signs
 int f3_block_chunks(int TV);                 // row chunks per clip of the block kernels (dbpart rows: chunks * N)
 int f3_bnrelu_bf16(const f3::BnReluArgs* a, hipStream_t s);
 // several independent column sums in one launch (each as f3_colsum_ld)

@@ -1126,7 +1126,24 @@ F3_DEV f32x4 quad_reduce(f32x4 v, float* lds, int C4) {
 // pooled-gradient form are template parameters for the same reason.
 constexpr int kRowU = 4;
 
-// out = relu(bn2(h) * a[n,c] + res), res = bn_r(r) | x | 0 ; optional pooled mean
+// ReLU sign words (BlockArgs::signs), thread-private: the three kernels below share one grid, one
+// tid -> (row, channel quad) map and one row walk, so a thread's trip covers the same kRowU rows x 4
+// channels in all of them. Bit 4u + e of the uint16 at
+//   signs[((n * chunks + chunk) * trips + trip) * 256 + tid],  trips = block_sign_trips(TV, chunks, C),
+// is (stored out > 0) for row u, channel e of that trip: 512 contiguous bytes per workgroup and trip,
+// no cross-lane traffic. Rows clamped past the chunk end repeat the last row's bits, so every word of a
+// trip that a thread runs is written whole; a trip a thread does not run (its first row is past the
+// chunk) has no word written and none read.
+__host__ __device__ inline int block_sign_trips(int TV, int chunks, int C) {
+  const int per = (TV + chunks - 1) / chunks, rows = kRowU * (256 / (C / 4));
+  return (per + rows - 1) / rows;
+}
+F3_DEV size_t block_sign_base(const BlockArgs& a) {
+  return ((size_t)blockIdx.y * a.chunks + blockIdx.x) * block_sign_trips(a.TV, a.chunks, a.C) * 256 + threadIdx.x;
+}
+
+// out = relu(bn2(h) * a[n,c] + res), res = bn_r(r) | x | 0 ; optional pooled mean; a.signs: the sign
+// words of the stored out (the bf16 mode compares the rounded value, which the backward would load)
 template <bool A16, int RES>
 __global__ __launch_bounds__(256) void block_out_kernel(BlockArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[1024];
@@ -1152,8 +1169,10 @@ __global__ __launch_bounds__(256) void block_out_kernel(BlockArgs a) {
   if (RES == RES_CONV) bn_coeff4(a.bnr, c0, scr, shr, mu, rs);
   const f32x4 av = *reinterpret_cast<const f32x4*>(a.att + (size_t)n * C + c0);
   f32x4 pool = {0.f, 0.f, 0.f, 0.f};
+  unsigned short* sgw = a.signs ? a.signs + block_sign_base(a) : nullptr;
   for (int mb = mb0; mb < r1; mb += kRowU * RP) {
     if (mb != mb0) F3_BO_LOADS(mb)
+    unsigned sg = 0;
 #pragma unroll
     for (int u = 0; u < kRowU; ++u) {
       f32x4 o;
@@ -1162,6 +1181,8 @@ __global__ __launch_bounds__(256) void block_out_kernel(BlockArgs a) {
         float rv = res[u][e];
         if (RES == RES_CONV) rv = rv * scr[e] + shr[e];
         o[e] = fmaxf((h[u][e] * sc2[e] + sh2[e]) * av[e] + rv, 0.f);
+        const float stored = A16 ? (float)(__bf16)o[e] : o[e];
+        sg |= (stored > 0.f ? 1u : 0u) << (4 * u + e);
       }
       st_act4<A16>(a.out, off[u], o);
       if (a.outb) {
@@ -1180,6 +1201,10 @@ __global__ __launch_bounds__(256) void block_out_kernel(BlockArgs a) {
         }
       }
       if (mb + u * RP < r1) pool += o;
+    }
+    if (sgw) {
+      *sgw = (unsigned short)sg;
+      sgw += 256;
     }
   }
 #undef F3_BO_LOADS
@@ -1200,7 +1225,8 @@ __global__ __launch_bounds__(256) void block_out_kernel(BlockArgs a) {
 //   dz = dout * (out > 0);  P1[n,c] = sum_tv dz;  P2[n,c] = sum_tv dz*xhat2
 //   conv residual: R[c] += (sum dz, sum dz*xhat_r)
 // DNC: the output gradient is the pooled-mean gradient dout_nc[n][c] broadcast * inv_tv
-template <bool A16, int RES, bool DNC>
+// SG: (out > 0) from block_out's sign words (one 2-B load per trip); `out` is not loaded
+template <bool A16, int RES, bool DNC, bool SG>
 __global__ __launch_bounds__(256) void block_bwd_reduce_kernel(BlockArgs a) {
   __shared__ __attribute__((aligned(16))) float lds[1024];
   const int C = a.C, C4 = C / 4, RP = 256 / C4, tid = threadIdx.x;
@@ -1210,13 +1236,21 @@ __global__ __launch_bounds__(256) void block_bwd_reduce_kernel(BlockArgs a) {
   // the first pass's rows are loaded before the coefficient prologue (they do not depend on it)
   const int mb0 = r0 + tid / C4;
   f32x4 o[kRowU], d[kRowU], h[kRowU], rr[kRowU];
-#define F3_BR_LOADS(MB)                                                          \
-  _Pragma("unroll") for (int u = 0; u < kRowU; ++u) {                            \
-    const size_t off = (size_t)min((MB) + u * RP, r1 - 1) * C + c0;              \
-    o[u] = ld_act4<A16>(a.out, off);                                             \
-    if (!DNC) d[u] = *reinterpret_cast<const f32x4*>(a.dout + off);              \
-    h[u] = ld_act4<A16>(a.h, off);                                               \
-    if (RES == RES_CONV) rr[u] = ld_act4<A16>(a.r, off);                         \
+  unsigned sg = 0;
+  const unsigned short* sgw = SG ? a.signs + block_sign_base(a) : nullptr;
+#define F3_BR_LOADS(MB)                                                            \
+  {                                                                                \
+    if (SG) {                                                                      \
+      sg = *sgw;                                                                   \
+      sgw += 256;                                                                  \
+    }                                                                              \
+    _Pragma("unroll") for (int u = 0; u < kRowU; ++u) {                            \
+      const size_t off = (size_t)min((MB) + u * RP, r1 - 1) * C + c0;              \
+      if (!SG) o[u] = ld_act4<A16>(a.out, off);                                    \
+      if (!DNC) d[u] = *reinterpret_cast<const f32x4*>(a.dout + off);              \
+      h[u] = ld_act4<A16>(a.h, off);                                               \
+      if (RES == RES_CONV) rr[u] = ld_act4<A16>(a.r, off);                         \
+    }                                                                              \
   }
   F3_BR_LOADS(mb0)
   float mu2[4], rs2[4], mur[4], rsr[4], sc[4], sh[4];
@@ -1232,7 +1266,8 @@ __global__ __launch_bounds__(256) void block_bwd_reduce_kernel(BlockArgs a) {
       const float w = mb + u * RP < r1 ? 1.f : 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float dz = o[u][e] > 0.f ? (DNC ? dbc[e] : d[u][e]) * w : 0.f;
+        const bool pos = SG ? (sg >> (4 * u + e)) & 1u : o[u][e] > 0.f;
+        const float dz = pos ? (DNC ? dbc[e] : d[u][e]) * w : 0.f;
         p1[e] += dz;
         p2[e] += dz * ((h[u][e] - mu2[e]) * rs2[e]);
         if (RES == RES_CONV) q2[e] += dz * ((rr[u][e] - mur[e]) * rsr[e]);
@@ -1279,7 +1314,8 @@ __global__ __launch_bounds__(256) void block_bwd_reduce_kernel(BlockArgs a) {
 }
 
 // dh = g2*rs2*(dz*a + e - D1/M - xhat2*D2/M);  residual: dr (conv) or dx = dz (identity)
-template <bool A16, int RES, bool DNC>
+// SG: as block_bwd_reduce_kernel
+template <bool A16, int RES, bool DNC, bool SG>
 __global__ __launch_bounds__(256) void block_bwd_apply_kernel(BlockArgs a) {
   const int C = a.C, C4 = C / 4, RP = 256 / C4, tid = threadIdx.x;
   const float invM = 1.f / (float)a.bn2.count;
@@ -1300,13 +1336,21 @@ __global__ __launch_bounds__(256) void block_bwd_apply_kernel(BlockArgs a) {
   const int mb0 = r0 + tid / C4;
   f32x4 o[kRowU], d[kRowU], h[kRowU], rr[kRowU];
   size_t off[kRowU];
-#define F3_BA_LOADS(MB)                                                          \
-  _Pragma("unroll") for (int u = 0; u < kRowU; ++u) {                            \
-    off[u] = (size_t)min((MB) + u * RP, r1 - 1) * C + c0;                        \
-    o[u] = ld_act4<A16>(a.out, off[u]);                                          \
-    if (!DNC) d[u] = *reinterpret_cast<const f32x4*>(a.dout + off[u]);           \
-    h[u] = ld_act4<A16>(a.h, off[u]);                                            \
-    if (RES == RES_CONV) rr[u] = ld_act4<A16>(a.r, off[u]);                      \
+  unsigned sg = 0;
+  const unsigned short* sgw = SG ? a.signs + block_sign_base(a) : nullptr;
+#define F3_BA_LOADS(MB)                                                            \
+  {                                                                                \
+    if (SG) {                                                                      \
+      sg = *sgw;                                                                   \
+      sgw += 256;                                                                  \
+    }                                                                              \
+    _Pragma("unroll") for (int u = 0; u < kRowU; ++u) {                            \
+      off[u] = (size_t)min((MB) + u * RP, r1 - 1) * C + c0;                        \
+      if (!SG) o[u] = ld_act4<A16>(a.out, off[u]);                                 \
+      if (!DNC) d[u] = *reinterpret_cast<const f32x4*>(a.dout + off[u]);           \
+      h[u] = ld_act4<A16>(a.h, off[u]);                                            \
+      if (RES == RES_CONV) rr[u] = ld_act4<A16>(a.r, off[u]);                      \
+    }                                                                              \
   }
   F3_BA_LOADS(mb0)
   float mu2[4], k2[4], m1[4], m2[4], rs2[4], mur[4], kr[4], n1[4], n2[4], rsr[4], sc[4], sh[4];
@@ -1346,7 +1390,8 @@ __global__ __launch_bounds__(256) void block_bwd_apply_kernel(BlockArgs a) {
       f32x4 dh, dr;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float dz = o[u][e] > 0.f ? (DNC ? dbc[e] : d[u][e]) : 0.f;
+        const bool pos = SG ? (sg >> (4 * u + e)) & 1u : o[u][e] > 0.f;
+        const float dz = pos ? (DNC ? dbc[e] : d[u][e]) : 0.f;
         const float xh = (h[u][e] - mu2[e]) * rs2[e];
         dh[e] = k2[e] * (dz * av[e] + ev[e] - m1[e] - xh * m2[e]);
         if (RES == RES_CONV) {
@@ -2635,13 +2680,22 @@ int f3_gcn_bias_bwd(const GcnBiasBwdArgs* a, hipStream_t s) {
 // measured no faster, profiles/r03_chunk_ab.txt)
 static int chunks_for(int TV) { return max(1, (TV + 95) / 96); }
 int f3_block_chunks(int TV) { return chunks_for(TV); }
+long long f3_block_sign_words(int N, int TV, int C) {
+  const int chunks = chunks_for(TV);
+  return (long long)chunks * N * block_sign_trips(TV, chunks, C) * 256;
+}
 
-// backward block kernels: instantiate on (activation type, residual kind, pooled gradient)
+// backward block kernels: instantiate on (activation type, residual kind, pooled gradient, sign words)
+template <bool A16, int RES, bool DNC, bool SG>
+static void launch_block_bwd0(const BlockArgs& a, bool reduce, hipStream_t s) {
+  const dim3 grid(a.chunks, a.N);
+  if (reduce) hipLaunchKernelGGL((block_bwd_reduce_kernel<A16, RES, DNC, SG>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((block_bwd_apply_kernel<A16, RES, DNC, SG>), grid, dim3(256), 0, s, a);
+}
 template <bool A16, int RES, bool DNC>
 static void launch_block_bwd1(const BlockArgs& a, bool reduce, hipStream_t s) {
-  const dim3 grid(a.chunks, a.N);
-  if (reduce) hipLaunchKernelGGL((block_bwd_reduce_kernel<A16, RES, DNC>), grid, dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((block_bwd_apply_kernel<A16, RES, DNC>), grid, dim3(256), 0, s, a);
+  if (a.signs) launch_block_bwd0<A16, RES, DNC, true>(a, reduce, s);
+  else launch_block_bwd0<A16, RES, DNC, false>(a, reduce, s);
 }
 template <bool A16, int RES>
 static void launch_block_bwd2(const BlockArgs& a, bool reduce, hipStream_t s) {

@@ -125,6 +125,13 @@ inline bool gcn_fwd_fused() {
   return on;
 }
 
+// F3_BLOCK_SIGNS=0: no ReLU sign words: block_out writes none and the block backward reads the block
+// output for (out > 0) (the A/B baseline of BlockArgs::signs); read once per process
+inline bool block_signs() {
+  static const bool on = !getenv("F3_BLOCK_SIGNS") || atoi(getenv("F3_BLOCK_SIGNS")) != 0;
+  return on;
+}
+
 // The only place that asks the shape predicates and the two switches (see LayerFmt).
 // next_res_conv: the next block has a residual conv, which reads this block's output as a GEMM operand.
 LayerFmt layer_fmt(int precision, int K, int V, int Ci, int C, int res, bool next_res_conv) {
@@ -371,6 +378,9 @@ struct LayerWs {
   // the side stream
   float *gpart = nullptr, *mixpart = nullptr;
   float* dbpart = nullptr;  // bf16x3: block_bwd_apply's dh / dres column-sum rows (tcn / residual bias grads)
+  // ReLU sign words of the block output (BlockArgs::signs): written by the training forward, read by
+  // the block backward instead of `out`; null with F3_BLOCK_SIGNS=0
+  unsigned short* signs = nullptr;
 };
 
 struct StreamWs {
@@ -459,6 +469,7 @@ void plan_stream(const Net& net, const StreamIdx& S, StreamWs& W, int N, Arena& 
     X.gpart = A.take<float>((size_t)f3_bn_bwd_parts(N, L.T_in * V, V) * V * C);
     if (x3) X.dbpart = A.take<float>((size_t)f3_block_chunks(L.T_out * V) * N * 2 * C);
     X.mixpart = A.take<float>((size_t)kMixParts * K * V * V);
+    if (block_signs()) X.signs = A.take<unsigned short>((size_t)f3_block_sign_words(N, L.T_out * V, C));
     if (F.dres_w) X.dres = reinterpret_cast<float*>(A.take<char>(Mo * C * F.dres_w));
     xin = X.out;
     // bf16 mode: the block output itself is stored bf16 (the next block's residual-conv operand);
@@ -815,6 +826,7 @@ int layer_forward(const Net& net, int si, int l, int N, int train, const Ptrs& q
   ba.part = W.detm;
   ba.act16 = hb;
   if (F.outb_w) { ba.outb = X.outb; ba.x3 = 1; }
+  ba.signs = train ? X.signs : nullptr;  // (the eval forward writes nothing for a backward)
   F3_TRY(f3_block_out(ba, s));
   if (train) {
     add_bnrun(run, q, L.bn1, X.bn1.fsum, X.bn1.fsq, Mi);
@@ -973,6 +985,7 @@ int layer_backward_main(const LayerCtx& c, hipStream_t s) {
   ba.dgamma2 = q.g(L.bn2.w); ba.dbeta2 = q.g(L.bn2.b);
   if (L.res == RES_CONV) { ba.dgammar = q.g(L.bnr.w); ba.dbetar = q.g(L.bnr.b); }
   ba.part = W.detm;
+  ba.signs = X.signs;  // (out > 0) from the forward's sign words: `out` is not read
   ba.no_colsum = c.ca_sums;  // (one launch less per layer)
   F3_TRY(f3_block_bwd_reduce(ba, s));
   ba.no_colsum = 0;
@@ -1801,6 +1814,7 @@ void* f3_net_debug_tensor(f3_net* net, int batch, void* workspace, int stream, i
   if (k == "h") return X.h;
   if (k == "r") return X.r;
   if (k == "out") return X.out;
+  if (k == "signs") return X.signs;
   if (k == "att") return X.att;
   if (k == "dh") return X.dh;
   if (k == "u") return X.u;

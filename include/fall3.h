@@ -447,6 +447,27 @@ int f3_gcn_dgrad_mix_x3(const void* dg3, const float* w, void* wpack, const floa
 int f3_gcn_fwd_mix_x3(const float* A_eff, const float* x, const float* w, void* wpack, const float* bias_v, void* z3,
                       float* g, double* st_sum, double* st_sq, int frames, int K, int V, int Cin, int C,
                       void* stream);
+/* The block tail as the step launches it, on caller-owned tensors: phases & 1 the forward
+ * out = relu(bn2(h) att + res) (res_kind 0 none, 1 identity x, 2 bn_r(r)), phases & 2 its backward (the
+ * P1 / P2 / Q2 reduction, then dh / dres). M = N TV rows of C channels; act16: h, r, x, out are bf16.
+ * bn2, bnr: rows [gamma | beta | mean | var] of C floats (the running-statistics form); bn2_b, bnr_b:
+ * rows [sum | sumsq] of C doubles (the backward's batch sums); att, e [N][C]; dout [M][C] fp32, or
+ * dout_nc [N][C], the gradient of the pooled mean (then dout is not read).
+ * signs: NULL, or sign_words >= N chunks trips 256 uint16 words, chunks = ceil(TV / 96),
+ * trips = ceil(ceil(TV / chunks) / (4 RP)), RP = 256 / (C / 4): the forward sets bit 4u + e of word
+ * [(n chunks + chunk) trips + trip][tid] to (stored out > 0) for row chunk_start + trip 4 RP +
+ * tid / (C/4) + u RP (clamped to the chunk's last row), channel 4 (tid % (C/4)) + e, for every trip whose
+ * u = 0 row lies in the chunk; the backward then reads those words and never out. With NULL it reads out.
+ * Outputs: part [chunks][3][N][C] (P1 | P2 | Q2 partial rows; Q2 rows written for res_kind 2 only);
+ * dh and (res_kind != 0) dres: fp32 [M][C], or with act16 bf16 (dres of res_kind 1 stays fp32), or with
+ * x3 rows [hi | lo] of 2C bf16 (again not the identity dres); dbpart NULL or [chunks][N][C | C] column
+ * sums of dh | dres; dgb [4][C] (dgamma2, dbeta2, dgamma_r, dbeta_r) is added to.
+ * (F3_BLOCK_SIGNS=0 makes the step run without the words; this entry follows its signs argument.) */
+int f3_block_signs_case(int phases, const void* h, const void* r, const void* x, const float* att, const float* e,
+                        const float* bn2, const float* bnr, const double* bn2_b, const double* bnr_b,
+                        const float* dout, const float* dout_nc, void* out, void* signs, long long sign_words,
+                        float* part, void* dh, void* dres, float* dbpart, float* dgb, int N, int TV, int C,
+                        int res_kind, int act16, int x3, void* stream);
 
 const char* f3_status_string(int status);
 
