@@ -36,7 +36,7 @@ EXPORTS = (
     "f3_optim_scalars_bytes", "f3_optim_step", "f3_optim_step_ranges", "f3_net_backward_optim", "f3_net_entry_nograd",
     "f3_metrics_bytes", "f3_metrics_reset", "f3_metrics_update", "f3_segment_norms_scratch_bytes", "f3_segment_norms",
     "f3_soft_ce_ex", "f3_net_loss_ex", "f3_grad_accumulate",
-    "f3_optim_hyper_bytes", "f3_optim_hyper_set", "f3_optim_step_hyper",
+    "f3_optim_hyper_bytes", "f3_optim_hyper_set", "f3_optim_step_hyper", "f3_optim_guard_offset",
 )
 
 F3_OK, F3_EINVAL, F3_EBATCH, F3_EHIP, F3_ESTATE, F3_EDEVICE = 0, 1001, 1002, 1003, 1004, 1005
@@ -52,7 +52,7 @@ class F3OptimConfig(ctypes.Structure):
                 + [(n, ctypes.c_double) for n in ("lr", "alpha", "eps", "momentum", "beta1", "beta2", "weight_decay",
                                                   "max_norm", "grad_scale")]
                 + [("nskip", ctypes.c_int), ("skip_lo", ctypes.c_int64 * OPT_MAX_SKIP),
-                   ("skip_len", ctypes.c_int64 * OPT_MAX_SKIP)])
+                   ("skip_len", ctypes.c_int64 * OPT_MAX_SKIP), ("skip_nonfinite", ctypes.c_int)])
 
 
 class F3TargcnConfig(ctypes.Structure):
@@ -106,6 +106,7 @@ def lib():
         "f3_net_status": (I, [P, I]),
         "f3_rmsprop_step": (I, [P, P, P, I64, F, F, F, F, P]),
         "f3_optim_scalars_bytes": (I64, []),
+        "f3_optim_guard_offset": (I64, []),
         "f3_optim_step": (I, [ctypes.POINTER(F3OptimConfig), P, P, P, P, I64, P, P]),
         "f3_optim_step_ranges": (I, [ctypes.POINTER(F3OptimConfig), P, P, P, P, I, ctypes.POINTER(I64),
                                      ctypes.POINTER(I64), P, P]),

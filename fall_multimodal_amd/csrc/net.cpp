@@ -1732,8 +1732,8 @@ int f3_net_backward_optim(f3_net* net, int N, float* params, const float* dout, 
   if (net->fused_opt < 0) fused_opt_plan(*net);
   if (net->nograd_skip.n < 0) return F3_EINVAL;
   // clipping: the norm needs every gradient, so one flat update after the join (as the layouts without
-  // contiguous per-layer ranges)
-  if (!net->fused_opt || o.max_norm > 0.0) {
+  // contiguous per-layer ranges); the non-finite guard decides on every gradient too
+  if (!net->fused_opt || o.max_norm > 0.0 || o.guard) {
     F3_TRY(net_backward(net, N, params, dout, grads, workspace, 0, stream, nullptr));
     F3_TRY(f3_optim_begin(o, net->nparam, s));
     return f3_optim_flat(o, net->nparam, net->nograd_skip, s);

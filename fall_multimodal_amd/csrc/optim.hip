@@ -14,6 +14,7 @@
 // graph, from the OptHyper device block when the kernel runs (f3_optim_step_hyper, optim_hyper_kernel):
 // lr_scheduler.step(e) (model/main.py:321-322) then takes effect on a replay. Both forms give the same bits.
 #include <cmath>
+#include <cstddef>
 
 #include "common.h"
 #include "sensor.h"
@@ -101,12 +102,15 @@ F3_DEV bool opt_skipped(const OptSkip& k, long long i) {
   return in;
 }
 
-// flat shape: float4 body + scalar tail over n floats, grid-stride (as rmsprop_kernel)
-template <int KIND>
+// flat shape: float4 body + scalar tail over n floats, grid-stride (as rmsprop_kernel). GUARD (the step's
+// skip_nonfinite): every thread reads the begin kernel's verdict and returns before its first load when
+// the step is skipped, so nothing is stored; without GUARD the test is not compiled in.
+template <int KIND, bool GUARD = false>
 __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, float* __restrict__ s0,
                                                     float* __restrict__ s1, const float* __restrict__ g,
                                                     long long n, OptArgs a, OptSkip skip,
                                                     const OptScalars* __restrict__ sc) {
+  if (GUARD && sc->last_skipped != 0) return;
   const double sg = a.gscale * (double)sc->clip_coef;
   const float bc1 = sc->bc1, bc2s = sc->bc2s;
   const long long n4 = n / 4;
@@ -133,11 +137,12 @@ __global__ __launch_bounds__(256) void optim_kernel(float* __restrict__ p, float
 // step's structure and stays an argument. A kernel of its own with the loop written again: moving the
 // loop into a function shared with optim_kernel changes that kernel's instruction schedule, and the
 // by-value kernels are to stay the code they were.
-template <int KIND>
+template <int KIND, bool GUARD = false>
 __global__ __launch_bounds__(256) void optim_hyper_kernel(float* __restrict__ p, float* __restrict__ s0,
                                                           float* __restrict__ s1, const float* __restrict__ g,
                                                           long long n, const OptHyper* __restrict__ h, int nesterov,
                                                           OptSkip skip, const OptScalars* __restrict__ sc) {
+  if (GUARD && sc->last_skipped != 0) return;
   const OptArgs a = opt_args_of(h->lr, h->alpha, h->eps, h->momentum, h->beta1, h->beta2, h->weight_decay,
                                 h->grad_scale, nesterov);
   const double sg = a.gscale * (double)sc->clip_coef;
@@ -205,10 +210,29 @@ __global__ __launch_bounds__(256) void gradnorm_partials_kernel(const float* __r
 
 // once per optimizer step, one workgroup: t += 1, the bias corrections in fp64 from the integer t, the
 // norm from the partials in index order, the clip coefficient (clip_grad_norm_: max_norm / (norm + 1e-6),
-// clamped to 1; a non-finite norm propagates as in torch)
+// clamped to 1; a non-finite norm propagates as in torch).
+// guard (skip_nonfinite): the partials are always summed, and the step is skipped iff the fp64 sum of
+// squares is not finite, which is exactly when some element is (an fp32 square is exact in fp64, the
+// squares are non-negative and n * FLT_MAX^2 is far below DBL_MAX). The fp32 grad_norm is not the test: a
+// finite gradient may have a norm above FLT_MAX. A skip leaves t and the bias corrections as they were,
+// writes clip_coef 0 and the non-finite norm, counts itself and sets last_skipped for the update launch.
 F3_DEV void optim_begin(OptScalars* __restrict__ sc, int adam, double b1, double b2, double max_norm,
-                        double gscale) {
+                        double gscale, int guard) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double sum = 0.0;
+  if (max_norm > 0.0 || guard)
+    for (int i = 0; i < kNormBlocks; ++i) sum += sc->partials[i];
+  const double nd = gscale * sqrt(sum);
+  if (guard) {
+    if (!isfinite(sum)) {
+      sc->clip_coef = 0.f;
+      sc->grad_norm = (float)nd;
+      sc->skipped = sc->skipped + 1;
+      sc->last_skipped = 1;
+      return;
+    }
+    sc->last_skipped = 0;
+  }
   const long long t = sc->t + 1;
   sc->t = t;
   float bc1 = 1.f, bc2s = 1.f;
@@ -220,27 +244,26 @@ F3_DEV void optim_begin(OptScalars* __restrict__ sc, int adam, double b1, double
   sc->bc2s = bc2s;
   float coef = 1.f, norm = 0.f;
   if (max_norm > 0.0) {
-    double sum = 0.0;
-    for (int i = 0; i < kNormBlocks; ++i) sum += sc->partials[i];
-    const double nd = gscale * sqrt(sum);
     const double c = max_norm / (nd + 1e-6);
     norm = (float)nd;
     coef = (float)(c > 1.0 ? 1.0 : c);
+  } else if (guard) {
+    norm = (float)nd;  // a by-product: the sum was formed anyway
   }
   sc->clip_coef = coef;
   sc->grad_norm = norm;
 }
 
 __global__ void optim_begin_kernel(OptScalars* __restrict__ sc, int adam, double b1, double b2, double max_norm,
-                                   double gscale) {
-  optim_begin(sc, adam, b1, b2, max_norm, gscale);
+                                   double gscale, int guard) {
+  optim_begin(sc, adam, b1, b2, max_norm, gscale, guard);
 }
 
-// The recorded form: the betas, max_norm and grad_scale from the block. Whether the step clips (the norm
-// partials were launched before this kernel) is structure: without it max_norm counts as 0.
-__global__ void optim_begin_hyper_kernel(OptScalars* __restrict__ sc, int adam, int clip,
+// The recorded form: the betas, max_norm and grad_scale from the block. Whether the step clips or guards
+// (the norm partials were launched before this kernel) is structure: without clip max_norm counts as 0.
+__global__ void optim_begin_hyper_kernel(OptScalars* __restrict__ sc, int adam, int clip, int guard,
                                          const OptHyper* __restrict__ h) {
-  optim_begin(sc, adam, h->beta1, h->beta2, clip ? h->max_norm : 0.0, h->grad_scale);
+  optim_begin(sc, adam, h->beta1, h->beta2, clip ? h->max_norm : 0.0, h->grad_scale, guard);
 }
 
 // one thread: the nine values into the block (f3_optim_hyper_set), launched eagerly on the caller's stream
@@ -320,17 +343,19 @@ int f3_optim_resolve(const f3_optim_config* c, float* p, float* s0, float* s1, c
   o->b1 = adam ? c->beta1 : 0.0; o->b2 = adam ? c->beta2 : 0.0;
   o->wd = c->weight_decay; o->max_norm = c->max_norm; o->gscale = c->grad_scale;
   o->p = p; o->s0 = s0; o->s1 = s1; o->g = g; o->sc = static_cast<OptScalars*>(scalars);
+  o->guard = c->skip_nonfinite != 0;
   return F3_OK;
 }
 
 int f3_optim_begin(const OptLaunch& o, long long n, hipStream_t s) {
   if (n < 0 || (uintptr_t)o.g % 16) return F3_EINVAL;
-  if (o.max_norm > 0.0) {
+  if (o.max_norm > 0.0 || o.guard) {
     hipLaunchKernelGGL(gradnorm_partials_kernel, dim3(kNormBlocks), dim3(256), 0, s, o.g, n, o.sc->partials);
     F3_LAUNCH_CHECK();
   }
   const int adam = o.kind == F3_OPT_ADAM || o.kind == F3_OPT_ADAMW;
-  hipLaunchKernelGGL(optim_begin_kernel, dim3(1), dim3(64), 0, s, o.sc, adam, o.b1, o.b2, o.max_norm, o.gscale);
+  hipLaunchKernelGGL(optim_begin_kernel, dim3(1), dim3(64), 0, s, o.sc, adam, o.b1, o.b2, o.max_norm, o.gscale,
+                     (int)o.guard);
   F3_LAUNCH_CHECK();
   return F3_OK;
 }
@@ -343,6 +368,15 @@ int f3_optim_begin(const OptLaunch& o, long long n, hipStream_t s) {
     case OK_ADAM: hipLaunchKernelGGL(KERNEL<OK_ADAM>, __VA_ARGS__); break;                  \
     default: hipLaunchKernelGGL(KERNEL<OK_ADAMW>, __VA_ARGS__); break;                      \
   }
+// the guarded instantiations (flat shapes only: the decision needs every gradient)
+#define F3_OPT_DISPATCH_GUARDED(VARIANT, KERNEL, ...)                                                     \
+  switch (VARIANT) {                                                                                      \
+    case OK_RMS: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<OK_RMS, true>), __VA_ARGS__); break;           \
+    case OK_SGD: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<OK_SGD, true>), __VA_ARGS__); break;           \
+    case OK_SGD0: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<OK_SGD0, true>), __VA_ARGS__); break;         \
+    case OK_ADAM: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<OK_ADAM, true>), __VA_ARGS__); break;         \
+    default: hipLaunchKernelGGL(HIP_KERNEL_NAME(KERNEL<OK_ADAMW, true>), __VA_ARGS__); break;             \
+  }
 
 int f3_optim_flat(const OptLaunch& o, long long n, const OptSkip& skip, hipStream_t s) {
   if (n < 0 || skip.n < 0 || skip.n > kOptSkip) return F3_EINVAL;
@@ -354,14 +388,20 @@ int f3_optim_flat(const OptLaunch& o, long long n, const OptSkip& skip, hipStrea
     return f3_rmsprop(o.p, o.s0, o.g, n, (float)o.lr, (float)o.alpha, (float)o.eps, (float)o.gscale, s);
   const OptArgs a = opt_args(o);
   const OptScalars* sc = o.sc;
-  F3_OPT_DISPATCH(opt_variant(o), optim_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, o.p, o.s0, o.s1, o.g, n, a,
-                  skip, sc);
+  if (o.guard) {
+    F3_OPT_DISPATCH_GUARDED(opt_variant(o), optim_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, o.p, o.s0, o.s1,
+                            o.g, n, a, skip, sc);
+  } else {
+    F3_OPT_DISPATCH(opt_variant(o), optim_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, o.p, o.s0, o.s1, o.g, n, a,
+                    skip, sc);
+  }
   F3_LAUNCH_CHECK();
   return F3_OK;
 }
 
 int f3_optim_ranges(const OptLaunch& o, const RmsRanges& r, hipStream_t s) {
-  if (o.max_norm > 0.0) return F3_EINVAL;  // the norm needs every gradient: flat update after the backward
+  // the norm and the guard's decision need every gradient: flat update after the backward
+  if (o.max_norm > 0.0 || o.guard) return F3_EINVAL;
   if (o.legacy_rms())
     return f3_rmsprop_ranges(o.p, o.s0, o.g, r, (float)o.lr, (float)o.alpha, (float)o.eps, (float)o.gscale, s);
   if (r.n < 0 || r.n > kRmsRanges) return F3_EINVAL;
@@ -383,6 +423,8 @@ int f3_optim_ranges(const OptLaunch& o, const RmsRanges& r, hipStream_t s) {
 extern "C" {
 
 int64_t f3_optim_scalars_bytes(void) { return (int64_t)sizeof(OptScalars); }
+
+int64_t f3_optim_guard_offset(void) { return (int64_t)offsetof(OptScalars, skipped); }
 
 int f3_optim_step(const f3_optim_config* cfg, float* params, float* state0, float* state1, const float* grads,
                   int64_t n, void* scalars, void* stream) {
@@ -419,25 +461,31 @@ int f3_optim_step_hyper(const f3_optim_config* cfg, float* params, float* state0
   if (((uintptr_t)params | (uintptr_t)state0 | (uintptr_t)state1 | (uintptr_t)grads) % 16) return F3_EINVAL;
   const OptHyper* h = static_cast<const OptHyper*>(hyper);
   hipStream_t s = (hipStream_t)stream;
-  // the structure, from cfg: the plain-RMSprop route, clipping on or off, the kernel variant
+  // the structure, from cfg: the plain-RMSprop route, clipping and the guard on or off, the kernel variant
   const bool clip = cfg->max_norm > 0.0;
-  if (cfg->kind == F3_OPT_RMSPROP && cfg->weight_decay == 0.0 && !clip)
+  const bool guard = cfg->skip_nonfinite != 0;
+  if (cfg->kind == F3_OPT_RMSPROP && cfg->weight_decay == 0.0 && !clip && !guard)
     return f3_rmsprop_hyper(params, state0, grads, n, h, s);  // skipped entries: as in f3_optim_flat
   if (!scalars || (uintptr_t)scalars % 8) return F3_EINVAL;
   OptScalars* sc = static_cast<OptScalars*>(scalars);
-  if (clip) {
+  if (clip || guard) {
     hipLaunchKernelGGL(gradnorm_partials_kernel, dim3(kNormBlocks), dim3(256), 0, s, grads, n, sc->partials);
     F3_LAUNCH_CHECK();
   }
   const int adam = cfg->kind == F3_OPT_ADAM || cfg->kind == F3_OPT_ADAMW;
-  hipLaunchKernelGGL(optim_begin_hyper_kernel, dim3(1), dim3(64), 0, s, sc, adam, (int)clip, h);
+  hipLaunchKernelGGL(optim_begin_hyper_kernel, dim3(1), dim3(64), 0, s, sc, adam, (int)clip, (int)guard, h);
   F3_LAUNCH_CHECK();
   if (n == 0) return F3_OK;
   const int variant = cfg->kind == F3_OPT_SGD && cfg->momentum == 0.0 ? (int)OK_SGD0 : cfg->kind;
   const int nesterov = cfg->nesterov != 0;
   const OptScalars* csc = sc;
-  F3_OPT_DISPATCH(variant, optim_hyper_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, params, state0, state1, grads,
-                  (long long)n, h, nesterov, skip, csc);
+  if (guard) {
+    F3_OPT_DISPATCH_GUARDED(variant, optim_hyper_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, params, state0,
+                            state1, grads, (long long)n, h, nesterov, skip, csc);
+  } else {
+    F3_OPT_DISPATCH(variant, optim_hyper_kernel, dim3(opt_grid(n / 4)), dim3(256), 0, s, params, state0, state1,
+                    grads, (long long)n, h, nesterov, skip, csc);
+  }
   F3_LAUNCH_CHECK();
   return F3_OK;
 }
@@ -447,7 +495,8 @@ int f3_optim_step_ranges(const f3_optim_config* cfg, float* params, float* state
                          void* stream) {
   OptLaunch o;
   F3_TRY(f3_optim_resolve(cfg, params, state0, state1, grads, scalars, &o));
-  if (nranges < 0 || nranges > kRmsRanges || (nranges && (!lo || !len)) || o.max_norm > 0.0) return F3_EINVAL;
+  if (nranges < 0 || nranges > kRmsRanges || (nranges && (!lo || !len)) || o.max_norm > 0.0 || o.guard)
+    return F3_EINVAL;
   RmsRanges r;
   r.n = nranges;
   for (int j = 0; j < nranges; ++j) {

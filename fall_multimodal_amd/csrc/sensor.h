@@ -155,6 +155,11 @@ struct OptScalars {               // the device block behind f3_optim_scalars_by
   long long t;
   float bc1, bc2s, clip_coef, grad_norm;
   double partials[kNormBlocks];
+  // the non-finite guard (f3_optim_config.skip_nonfinite), at f3_optim_guard_offset(): written by guarded
+  // steps only; last_skipped is the word every guarded update launch reads before it touches anything
+  long long skipped;
+  int last_skipped;
+  int pad;
 };
 constexpr int kOptSkip = 4;
 struct OptSkip {
@@ -169,11 +174,13 @@ struct OptLaunch {
   float *p, *s0, *s1;
   const float* g;
   OptScalars* sc;
-  bool legacy_rms() const { return kind == 0 && wd == 0.0 && max_norm == 0.0; }  // rmsprop_kernel's bits
+  bool guard = false;  // skip_nonfinite: the begin kernel decides, the guarded update kernels obey
+  bool legacy_rms() const { return kind == 0 && wd == 0.0 && max_norm == 0.0 && !guard; }  // rmsprop_kernel's bits
 };
 int f3_optim_resolve(const f3_optim_config* cfg, float* p, float* s0, float* s1, const float* g, void* scalars,
                      OptLaunch* o);
-// [norm partials over g[0..n) when max_norm > 0,] then the begin kernel (t += 1, step scalars)
+// [norm partials over g[0..n) when max_norm > 0 or the guard is on,] then the begin kernel (t += 1, step
+// scalars; guarded: the skip decision, t left alone on a skip)
 int f3_optim_begin(const OptLaunch& o, long long n, hipStream_t s);
 int f3_optim_flat(const OptLaunch& o, long long n, const OptSkip& skip, hipStream_t s);
 int f3_optim_ranges(const OptLaunch& o, const RmsRanges& r, hipStream_t s);

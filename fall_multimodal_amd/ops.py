@@ -326,10 +326,12 @@ def _(param, square_avg, grad, lr, alpha, eps, scale):
 # SGD / Adam / AdamW / RMSprop with weight decay, optional grad-norm clipping (in place)
 # ---------------------------------------------------------------------------------------------
 def optim_config(kind: int, nesterov: bool, lr: float, alpha: float, eps: float, momentum: float, beta1: float,
-                 beta2: float, weight_decay: float, max_norm: float, grad_scale: float, skip=()):
-    """f3_optim_config from Python values; skip = flat [lo0, len0, lo1, len1, ...] of the no-gradient ranges."""
+                 beta2: float, weight_decay: float, max_norm: float, grad_scale: float, skip=(), skip_nonfinite=False):
+    """f3_optim_config from Python values; skip = flat [lo0, len0, lo1, len1, ...] of the no-gradient ranges;
+    skip_nonfinite: the update is skipped on the device when the gradient holds an inf or NaN (guard_views)."""
     c = _lib.F3OptimConfig()
     c.kind, c.nesterov = int(kind), int(bool(nesterov))
+    c.skip_nonfinite = int(bool(skip_nonfinite))
     c.lr, c.alpha, c.eps, c.momentum = lr, alpha, eps, momentum
     c.beta1, c.beta2, c.weight_decay, c.max_norm, c.grad_scale = beta1, beta2, weight_decay, max_norm, grad_scale
     if len(skip) % 2 or len(skip) // 2 > _lib.OPT_MAX_SKIP:
@@ -349,6 +351,13 @@ def scalar_views(scalars: Tensor):
     """(t int64[1], bias_correction1, bias_correction2_sqrt, clip_coef, grad_norm: fp32[1] each) views of a
     step-scalar block, in the layout include/fall3.h documents."""
     return (scalars[0:2].view(torch.int64), scalars[2:3], scalars[3:4], scalars[4:5], scalars[5:6])
+
+
+def guard_views(scalars: Tensor):
+    """(skipped int64[1], last_skipped int32[1]) views of a step-scalar block: the number of updates a
+    guarded step (skip_nonfinite) has skipped since the block was zeroed, and whether the last one was."""
+    o = int(lib().f3_optim_guard_offset()) // 4
+    return scalars[o:o + 2].view(torch.int64), scalars[o + 2:o + 3].view(torch.int32)
 
 
 HYPER_FIELDS = ("lr", "alpha", "eps", "momentum", "beta1", "beta2", "weight_decay", "max_norm", "grad_scale")

@@ -162,10 +162,28 @@ class TrainStep:
     Which calls update follows the reference's rule (accum_updates) from begin_epoch(num_batches) on, or
     `update=True / False` per call; `pending` counts the micro-batches in `accum`, zero_grad() discards
     them. steps_taken() and the checkpoint count updates. At 1 (the default) nothing changes: no `accum`,
-    the same launches, the per-layer fused update included."""
+    the same launches, the per-layer fused update included.
+
+    `skip_nonfinite` (what GradScaler.step does for an fp32 run, model/main.py:281): True applies the
+    optimizer update of a call if and only if every element of the gradient it consumes (`grads`, or
+    `accum` on an update call, after the all-reduce) is finite; otherwise the parameters, every state
+    buffer and the device step count keep their bits. The decision is taken on the device from the fp64
+    sum of squares (include/fall3.h), with no host sync, eager or replayed. `skipped` (int64) and
+    `last_skipped` (int32) are 1-element device views, skipped_steps() the host count (a sync); after a
+    skip `clip_coef` is 0 and `grad_norm` inf or NaN, after an applied step `grad_norm` is the norm even
+    without max_norm. steps_taken() and the checkpoint count applied updates only. A skipped
+    accumulating update still discards `accum`, as zero_grad() after a skipped scaler step does; BN
+    running statistics of the bad batch's forward are not rolled back (nor does torch). Every kind then
+    runs f3_optim_step / f3_net_backward_optim with one flat update after the backward, plain RMSprop
+    included. The setting is fixed for the life of the step (read-only). False (the default) issues
+    exactly the launches the step always issued."""
 
     def __init__(self, model, batch, lr=1e-3, alpha=0.99, eps=1e-8, process_group=None, optimizer=None,
-                 phased=None, force_sync=False, max_norm=None, metrics=None, label_smoothing=0.0, accum_iter=1):
+                 phased=None, force_sync=False, max_norm=None, metrics=None, label_smoothing=0.0, accum_iter=1,
+                 skip_nonfinite=False):
+        if not isinstance(skip_nonfinite, bool):
+            raise ValueError(f"TrainStep: skip_nonfinite must be True or False, got {skip_nonfinite!r}")
+        self._skip_nonfinite = skip_nonfinite
         self.label_smoothing, self.accum_iter = check_step_args(label_smoothing, accum_iter)
         if self.accum_iter > 1 and phased:
             raise ValueError("TrainStep: an accumulating step runs the whole backward per micro-batch (phased=True "
@@ -190,6 +208,8 @@ class TrainStep:
         # step scalars (f3_optim_scalars_bytes): device step count, bias corrections, clip coefficient, norm
         self.scalars = ops.optim_scalars(dev)
         self.step_count, _, _, self.clip_coef, self.grad_norm = ops.scalar_views(self.scalars)
+        # the guard words (skip_nonfinite): updates skipped so far, and whether the last one was
+        self.skipped, self.last_skipped = ops.guard_views(self.scalars)
         self._legacy_steps = 0  # steps of the plain-RMSprop launches (which keep no device count)
         self._graph_legacy = False
         # a captured step's hyper-parameter block (f3_optim_hyper_bytes), the structure its optimizer graph
@@ -308,9 +328,16 @@ class TrainStep:
             return self.optimizer.param_groups[0]
         return {"lr": self.lr, "alpha": self.alpha, "eps": self.eps}
 
+    @property
+    def skip_nonfinite(self):
+        """Whether the step skips an update on a non-finite gradient: fixed at construction."""
+        return self._skip_nonfinite
+
     def _legacy(self, group):
-        """Plain RMSprop (no decay, no clipping): the launches of f3_rmsprop_step / f3_net_backward_rmsprop."""
-        return self.kind == "rmsprop" and not group.get("weight_decay", 0) and not self.max_norm
+        """Plain RMSprop (no decay, no clipping, no guard): the launches of f3_rmsprop_step /
+        f3_net_backward_rmsprop."""
+        return (self.kind == "rmsprop" and not group.get("weight_decay", 0) and not self.max_norm
+                and not self._skip_nonfinite)
 
     def _config(self, group, grad_scale):
         _optim.check_supported(self.kind, group)
@@ -320,7 +347,7 @@ class TrainStep:
                 self._state[k] = torch.zeros_like(self.grads)
                 setattr(self, k, self._state[k])
         cfg = ops.optim_config(max_norm=float(self.max_norm or 0.0), grad_scale=grad_scale, skip=self._skip,
-                               **_optim.hyper(self.kind, group))
+                               skip_nonfinite=self._skip_nonfinite, **_optim.hyper(self.kind, group))
         st = [self._state[k] for k in keys] + [None, None]
         return cfg, st[0], st[1]
 
@@ -591,6 +618,11 @@ class TrainStep:
     def steps_taken(self):
         """Optimizer steps so far (reads the device count: a host sync)."""
         return int(self.step_count.item()) + self._legacy_steps
+
+    def skipped_steps(self):
+        """Updates skipped for a non-finite gradient so far (skip_nonfinite; reads the device count: a host
+        sync). steps_taken() and the checkpoint's `step` count the applied ones only."""
+        return int(self.skipped.item())
 
     def optimizer_state_dict(self):
         """torch.optim.<kind>(model.parameters()).state_dict() of this step's optimizer state: loads into

@@ -188,6 +188,7 @@ typedef struct f3_optim_config {
   double grad_scale;   /* 1.0 = torch semantics; 1/world after a summed all-reduce */
   int nskip;           /* <= F3_OPT_MAX_SKIP ranges that never receive a gradient */
   int64_t skip_lo[F3_OPT_MAX_SKIP], skip_len[F3_OPT_MAX_SKIP];
+  int skip_nonfinite;  /* nonzero: skip the update when the gradient is not finite (below); 0 = off */
 } f3_optim_config;
 /* The step scalars: a device block of f3_optim_scalars_bytes() bytes (8-byte aligned, zeroed by the
  * caller before the first step) that each step's one-workgroup "begin" kernel rewrites and every
@@ -195,17 +196,42 @@ typedef struct f3_optim_config {
  * graph advances it) at byte 0; fp32 1/(1-beta1^t), 1/sqrt(1-beta2^t) (fp64 from t, rounded once),
  * clip_coef = min(1, max_norm/(norm + 1e-6)) and grad_norm = grad_scale * ||grads||_2 at bytes 8, 12,
  * 16, 20 (clip_coef 1, grad_norm 0 with max_norm 0); then the norm's per-workgroup fp64 partial sums,
- * added in index order (no float atomics: same bits every run). */
+ * added in index order (no float atomics: same bits every run); then, at f3_optim_guard_offset(), the
+ * guard words: int64 skipped and, 8 bytes on, int32 last_skipped. */
 int64_t f3_optim_scalars_bytes(void);
+/* ---- skip_nonfinite: the update is applied iff every element of the gradient it consumes is finite ----
+ * What torch.cuda.amp.GradScaler.step does for an inf/NaN gradient (the reference builds one,
+ * TRAIN.USE_SCALER, model/main.py:281), decided on the device with no host sync, so it holds for a
+ * replayed HIP graph as well. Off (0) every launch and every bit are as without the field.
+ * The test: the gradient is non-finite iff the fp64 sum of squares over grads[0..n), the one the norm
+ * forms (per-workgroup partials added in index order), is not finite. That is exact: an fp32 square is
+ * exact in fp64, squares are non-negative, and n * FLT_MAX^2 is far below DBL_MAX, so the sum is inf/NaN
+ * exactly when some element is. The fp32 grad_norm is not the test: a finite gradient whose norm exceeds
+ * FLT_MAX is applied.
+ * A skipped step: params, state0 and state1 keep their bits (the update launch stores nothing: every
+ * thread reads last_skipped and returns); t is not advanced, so Adam's bias corrections at the next
+ * applied step are those of t + 1; clip_coef = 0.0; grad_norm = (float)(grad_scale * sqrt(sum)), inf or
+ * NaN; skipped (the number of skipped updates since the block was zeroed) += 1; last_skipped = 1.
+ * An applied step: last_skipped = 0, skipped unchanged; t, the bias corrections and clip_coef as without
+ * the guard; grad_norm is written even with max_norm 0 (the sum is formed anyway). Parameters and states
+ * are bit for bit those of the unguarded flat f3_optim_step with the same clip_coef; plain RMSprop (no
+ * decay, no clipping) runs the kernel it runs with max_norm set, so its bits are those of the unguarded
+ * step with a max_norm large enough that clip_coef == 1. All sums have a fixed order and there are no
+ * float atomics: the same inputs give the same bits, and the same decision, on every run and every rank.
+ * f3_optim_step, f3_optim_step_hyper and f3_net_backward_optim honour it (the last with one flat update
+ * after the join, as with clipping); f3_optim_step_ranges returns F3_EINVAL: the decision needs every
+ * gradient. scalars is then required for every kind. Unguarded steps never write the guard words. */
+int64_t f3_optim_guard_offset(void); /* byte offset of `skipped` in the step scalars; last_skipped at + 8 */
 /* optimizer.step() (model/main.py:127), preceded by clip_grad_norm_ when max_norm > 0 (root
  * main.py:108-113): [norm partials], begin, one flat update over n floats. grads are not modified
  * (the clip coefficient is a factor inside the update). F3_OPT_RMSPROP with weight_decay 0 and
- * max_norm 0 launches f3_rmsprop_step's kernel (same bits). */
+ * max_norm 0 launches f3_rmsprop_step's kernel (same bits), unless skip_nonfinite is set: a guarded step
+ * always runs norm partials, begin and the guarded update. */
 int f3_optim_step(const f3_optim_config* cfg, float* params, float* state0, float* state1, const float* grads,
                   int64_t n, void* scalars, void* stream);
 /* The same update over nranges <= 8 ranges (offsets / lengths in floats, multiples of 4) of the flat
  * buffers in one launch, as the per-layer updates inside f3_net_backward_optim issue it; max_norm
- * must be 0. Elements outside the ranges are untouched. */
+ * and skip_nonfinite must be 0. Elements outside the ranges are untouched. */
 int f3_optim_step_ranges(const f3_optim_config* cfg, float* params, float* state0, float* state1,
                          const float* grads, int nranges, const int64_t* lo, const int64_t* len, void* scalars,
                          void* stream);
@@ -219,7 +245,8 @@ int f3_optim_step_ranges(const f3_optim_config* cfg, float* params, float* state
  * expressions f3_optim_step evaluates on the host, so both forms give the same bits on the same values.
  * What a recorded step cannot take from the block is its structure, which launches run and which kernel
  * variant: the kind, momentum zero or not, nesterov, max_norm zero or not, and RMSprop with weight_decay
- * 0 and max_norm 0 (f3_rmsprop_step's kernel). The configuration argument supplies those. */
+ * 0 and max_norm 0 (f3_rmsprop_step's kernel), skip_nonfinite on or off. The configuration argument
+ * supplies those. */
 int64_t f3_optim_hyper_bytes(void);
 /* lr_scheduler.step(e) (model/main.py:321-322), or any other change of param_groups[0] / TRAIN.MAX_NORM /
  * the world size, made visible to the recorded update: checks cfg's kind and values as f3_optim_step
@@ -232,7 +259,7 @@ int f3_optim_hyper_set(const f3_optim_config* cfg, void* hyper, void* stream);
  * f3_optim_step issues them: [norm partials], begin, one flat update over n floats, each in the form that
  * reads its values from `hyper`. From cfg only the structure (above) and the skip ranges are taken; its
  * lr, alpha, eps, betas, weight_decay, grad_scale and the magnitudes of momentum and max_norm are ignored.
- * RMSprop with weight_decay 0 and max_norm 0 in cfg is f3_rmsprop_step's kernel reading (float) lr,
+ * RMSprop with weight_decay 0, max_norm 0 and skip_nonfinite 0 in cfg is f3_rmsprop_step's kernel reading (float) lr,
  * alpha, eps, grad_scale from the block: as that call it touches no scalars (scalars may be NULL) and
  * keeps no step count. Same bits as f3_optim_step / f3_rmsprop_step given the block's values. */
 int f3_optim_step_hyper(const f3_optim_config* cfg, float* params, float* state0, float* state1, const float* grads,
@@ -240,7 +267,7 @@ int f3_optim_step_hyper(const f3_optim_config* cfg, float* params, float* state0
 /* loss.backward(); [clip_grad_norm_;] optimizer.step() (model/main.py:115-127) in one call: the
  * generalisation of f3_net_backward_rmsprop. Without clipping the begin kernel runs before the
  * private queues fork and each skeleton layer's update is issued on the queue that finishes its
- * gradients; with clipping (the norm needs every gradient) one flat update follows the join. The
+ * gradients; with clipping or skip_nonfinite (both need every gradient) one flat update follows the join. The
  * net's no-gradient entries are skipped (cfg's own skip list is ignored). */
 int f3_net_backward_optim(f3_net* net, int batch, float* params, const float* dout, float* grads, float* state0,
                           float* state1, void* scalars, void* workspace, const f3_optim_config* cfg, void* stream);

@@ -3,8 +3,11 @@ default bf16x3, the headline mode), for kernel traces:
     rocprofv3 --kernel-trace -d gpurun_out/step -o run -- python tools/step_only.py [steps] [autograd]
     python tools/timeline.py gpurun_out/step/run_results.db --list
 With `autograd` the step is the reference loop body through the custom ops instead of TrainStep
-(opt.zero_grad(); CrossEntropyLoss()(model(x, s), y).backward(); f3.RMSprop.step(), model/main.py:112-127)."""
+(opt.zero_grad(); CrossEntropyLoss()(model(x, s), y).backward(); f3.RMSprop.step(), model/main.py:112-127).
+With `guard` it times TrainStep(skip_nonfinite=True) against the default step in one process, eager and
+captured: windows of [steps] steps, the two alternating, the median window of each (ms/step)."""
 import os
+import statistics
 import sys
 import time
 
@@ -13,7 +16,42 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 
 
+def guard_cost(steps, rounds=7):
+    import fall_multimodal_amd as f3
+    from oracle.prng import synthetic_batch
+    dev = torch.device("cuda")
+    B, V, S, C = 256, 18, 6, 11
+    sk, se, lb = (torch.from_numpy(x).to(dev) for x in synthetic_batch(B, V, C, S, 100))
+    for captured in (False, True):
+        runs = {}
+        for guard in (False, True):
+            model = f3.TwoStreamSTGCAN_BiLSTM(3, {"layout": "coco_mmpose", "strategy": "spatial"}, C, S, device=dev,
+                                              precision=os.environ.get("F3_STEP_PREC", "bf16x3"))
+            step = f3.TrainStep(model, B, lr=1e-3, skip_nonfinite=guard)
+            if captured:
+                step.capture(sk, se, step.prepare(sk, se, lb))
+            for _ in range(5):
+                step(sk, se, lb)
+            runs[guard] = (step, [])
+        torch.cuda.synchronize()
+        for _ in range(rounds):
+            for guard in (False, True):
+                step, times = runs[guard]
+                t0 = time.perf_counter()
+                for _ in range(steps):
+                    step(sk, se, lb)
+                torch.cuda.synchronize()
+                times.append((time.perf_counter() - t0) / steps * 1e3)
+        assert runs[True][0].skipped_steps() == 0 and runs[True][0].steps_taken() == 5 + rounds * steps
+        off, on = (runs[g][1] for g in (False, True))
+        print(f"{'captured' if captured else 'eager'}: guard off {statistics.median(off):.3f} ms/step "
+              f"(min {min(off):.3f} max {max(off):.3f}), guard on {statistics.median(on):.3f} ms/step "
+              f"(min {min(on):.3f} max {max(on):.3f}); {rounds} windows of {steps} steps each, alternating")
+
+
 def main():
+    if len(sys.argv) > 2 and sys.argv[2] == "guard":
+        return guard_cost(int(sys.argv[1]))
     import fall_multimodal_amd as f3
     from oracle.prng import synthetic_batch
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 8
