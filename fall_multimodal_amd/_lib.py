@@ -37,6 +37,7 @@ EXPORTS = (
     "f3_metrics_bytes", "f3_metrics_reset", "f3_metrics_update", "f3_segment_norms_scratch_bytes", "f3_segment_norms",
     "f3_soft_ce_ex", "f3_net_loss_ex", "f3_grad_accumulate",
     "f3_optim_hyper_bytes", "f3_optim_hyper_set", "f3_optim_step_hyper", "f3_optim_guard_offset",
+    "f3_ema_state_bytes", "f3_ema_set_decay", "f3_ema_update",
 )
 
 F3_OK, F3_EINVAL, F3_EBATCH, F3_EHIP, F3_ESTATE, F3_EDEVICE = 0, 1001, 1002, 1003, 1004, 1005
@@ -123,6 +124,9 @@ def lib():
         "f3_soft_ce_ex": (I, [P, P, P, I, I, F, P, P, P]),
         "f3_net_loss_ex": (I, [P, I, P, P, F, P, P, P]),
         "f3_grad_accumulate": (I, [P, P, I64, P, P]),
+        "f3_ema_state_bytes": (I64, []),
+        "f3_ema_set_decay": (I, [P, ctypes.c_double, P]),
+        "f3_ema_update": (I, [P, P, I64, P, P]),
         "f3_conv_forward": (I, [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P]),
         "f3_status_string": (ctypes.c_char_p, [I]),
         "f3_net_debug_tensor": (P, [P, I, P, I, I, ctypes.c_char_p]),

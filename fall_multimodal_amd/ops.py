@@ -374,6 +374,17 @@ def hyper_views(block: Tensor):
     return block.view(torch.float64)[:len(HYPER_FIELDS)]
 
 
+def ema_state(device):
+    """A zeroed EMA block (f3_ema_state_bytes) as an int64 tensor; f3_ema_set_decay writes its decay, every
+    f3_ema_update reads it and advances its count; see ema_views."""
+    return torch.zeros(int(lib().f3_ema_state_bytes()) // 8, dtype=torch.int64, device=device)
+
+
+def ema_views(block: Tensor):
+    """(n_averaged int64[1], decay fp64[1]) views of an EMA block, in the layout include/fall3.h documents."""
+    return block[0:1], block[1:2].view(torch.float64)
+
+
 @torch.library.custom_op("fall3::optim_", mutates_args=("param", "state0", "state1", "scalars"))
 def optim_(param: Tensor, state0: Tensor, state1: Tensor, scalars: Tensor, grad: Tensor, kind: int, nesterov: bool,
            lr: float, alpha: float, eps: float, momentum: float, beta1: float, beta2: float, weight_decay: float,

@@ -17,6 +17,7 @@ per-rank (the reference's per-device batch semantics).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 
@@ -105,6 +106,16 @@ def check_step_args(label_smoothing=0.0, accum_iter=1):
     return float(label_smoothing), int(accum_iter)
 
 
+def check_ema_decay(ema_decay):
+    """TrainStep's check of its averaging setting (no device needed): a number in [0, 1], the range in which
+    get_ema_multi_avg_fn's lerp stays between the average and the parameters. Returns the float."""
+    if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float, np.integer, np.floating)):
+        raise ValueError(f"TrainStep: ema_decay must be a number in [0, 1], got {ema_decay!r}")
+    if not 0.0 <= float(ema_decay) <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError(f"TrainStep: ema_decay must be in [0, 1], got {ema_decay!r}")
+    return float(ema_decay)
+
+
 def accum_updates(num_batches, accum_iter):
     """Which batches of an epoch end with optimizer.step() and model.zero_grad(): the reference's
     test `i % accum_iter == 0 or i + 1 == len(dataloader)` with i counted from the epoch's start
@@ -176,14 +187,32 @@ class TrainStep:
     running statistics of the bad batch's forward are not rolled back (nor does torch). Every kind then
     runs f3_optim_step / f3_net_backward_optim with one flat update after the backward, plain RMSprop
     included. The setting is fixed for the life of the step (read-only). False (the default) issues
-    exactly the launches the step always issued."""
+    exactly the launches the step always issued.
+
+    `ema_decay` (torch.optim.swa_utils.AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay)), or
+    timm's ModelEma; the reference's loop has no averaging): a number in [0, 1] keeps one averaged copy of the
+    parameters in the flat `ema` (a copy of the parameters at construction, as AveragedModel deep-copies) and
+    advances it with one launch pair (ema_update(): f3_ema_update) after every optimizer update, on the
+    stream the update ran on: eager on all three routes, on the update calls of an accumulating step, and
+    inside the optimizer graph of a captured one. The first update copies the parameters, every later one
+    is ema + (1 - decay) (p - ema) in fp64, rounded once (include/fall3.h); BatchNorm buffers are not
+    averaged (use_buffers=False). The count (`n_averaged`, a 1-element int64 device view) and the decay live
+    in the device block `ema_state` and are read when the launch runs: a replay advances the count, and
+    `step.ema_decay = d` (one eager launch, never inside a capture) is followed by the next replay. A
+    skip_nonfinite skip does not suppress the EMA update: torch's loop calls ema.update_parameters(model)
+    whether or not scaler.step applied, so the average moves toward the unchanged parameters and n_averaged
+    advances. Data parallel: no collective, every rank averages identical parameters with a deterministic
+    kernel. The average is used through ema_state_dict() (model.state_dict() with the averaged parameters),
+    `with step.swap_ema():` (the model holds the averaged weights inside it, same pointers), and
+    ema_checkpoint() / load_ema_checkpoint(). None (the default): no buffer, no block, no launch."""
 
     def __init__(self, model, batch, lr=1e-3, alpha=0.99, eps=1e-8, process_group=None, optimizer=None,
                  phased=None, force_sync=False, max_norm=None, metrics=None, label_smoothing=0.0, accum_iter=1,
-                 skip_nonfinite=False):
+                 ema_decay=None, skip_nonfinite=False):
         if not isinstance(skip_nonfinite, bool):
             raise ValueError(f"TrainStep: skip_nonfinite must be True or False, got {skip_nonfinite!r}")
         self._skip_nonfinite = skip_nonfinite
+        self._ema_decay = None if ema_decay is None else check_ema_decay(ema_decay)
         self.label_smoothing, self.accum_iter = check_step_args(label_smoothing, accum_iter)
         if self.accum_iter > 1 and phased:
             raise ValueError("TrainStep: an accumulating step runs the whole backward per micro-batch (phased=True "
@@ -273,6 +302,15 @@ class TrainStep:
         # world 1: the RMSprop update per layer inside the backward (F3_FUSED_OPT=0: one launch after it)
         self.fused_optimizer = (not self.sync.active and self.accum is None
                                 and os.environ.get("F3_FUSED_OPT", "1") != "0")
+        # the parameter average (ema_decay): the flat copy, its device block (f3_ema_state_bytes: the count
+        # and the decay, read by every update when it runs) and whether swap_ema() holds the model's weights
+        self.ema = self.ema_state = self.n_averaged = None
+        self._ema_swapped = False
+        if self._ema_decay is not None:
+            self.ema = model.flat_parameters().detach().clone()
+            self.ema_state = ops.ema_state(dev)
+            self.n_averaged, _ = ops.ema_views(self.ema_state)
+            self._ema_write(self._ema_decay)
 
     # -- the pieces ------------------------------------------------------------
     def prepare(self, skel, sensor, label):
@@ -407,6 +445,116 @@ class TrainStep:
         if values != self._hyper_values:
             self._hyper_write(values)
 
+    # -- the parameter average (ema_decay) -----------------------------------------------
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise ValueError(f"TrainStep.{what} needs ema_decay (this step keeps no parameter average)")
+
+    def _ema_write(self, decay):
+        """One eager launch on the current stream (f3_ema_set_decay), ordered before the next update or replay."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TrainStep: the EMA decay is written eagerly, never inside a capture")
+        check(lib().f3_ema_set_decay(ptr(self.ema_state), decay, stream_handle()), "ema decay")
+        self._ema_decay = decay
+
+    @property
+    def ema_decay(self):
+        """The decay in force (None: the step keeps no average). Setting it validates the value and writes
+        it to the device block with one eager launch: the next update follows it, replayed ones included."""
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, value):
+        self._need_ema("ema_decay")
+        self._ema_write(check_ema_decay(value))
+
+    def ema_update(self):
+        """ema_model.update_parameters(model): the one launch pair (f3_ema_update) on the current stream, the
+        lerp over the flat parameters and then n_averaged += 1. The step issues it after every optimizer update."""
+        self._need_ema("ema_update()")
+        flat = self.model.flat_parameters()
+        check(lib().f3_ema_update(ptr(self.ema), ptr(flat), flat.numel(), ptr(self.ema_state), stream_handle()),
+              "ema update")
+
+    def ema_state_dict(self):
+        """model.state_dict() (keys, order, shapes) with the parameters taken from `ema`, as copies; the
+        buffers are the model's current ones (use_buffers=False keeps them in sync with the model). Loads
+        into the reference's module, and as {"model_weight": ...} through evaluate.load_best."""
+        self._need_ema("ema_state_dict()")
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.ema_state_dict() inside swap_ema(): `ema` holds the raw weights there")
+        views = {name: (shape, off) for name, shape, off in self.model.param_views()}
+        sd = self.model.state_dict()
+        out = type(sd)()
+        for k, v in sd.items():
+            if k in views:
+                shape, off = views[k]
+                out[k] = self.ema[off:off + int(np.prod(shape))].view(tuple(shape)).clone()
+            else:
+                out[k] = v.detach().clone()
+        return out
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """Exchange the contents of model.flat_parameters() and `ema` in place, and exchange them back on
+        exit, also when the body raises. Pointers do not change, so captured graphs and the p.grad views
+        stay valid; evaluate.valid_device(model, loader) / test_device inside it evaluate the averaged
+        weights unchanged. Calling the step inside the context raises RuntimeError."""
+        self._need_ema("swap_ema()")
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.swap_ema() does not nest")
+        self._ema_exchange()
+        self._ema_swapped = True
+        try:
+            yield self.model
+        finally:
+            self._ema_exchange()
+            self._ema_swapped = False
+
+    def _ema_exchange(self):
+        flat = self.model.flat_parameters()
+        with torch.no_grad():
+            held = flat.detach().clone()
+            flat.copy_(self.ema)
+            self.ema.copy_(held)
+
+    def ema_checkpoint(self):
+        """{"n_averaged": int, "decay": float, "params": {name: cpu tensor}} in model.named_parameters() order
+        (reads the device count: a host sync)."""
+        self._need_ema("ema_checkpoint()")
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.ema_checkpoint() inside swap_ema(): `ema` holds the raw weights there")
+        views = {name: (shape, off) for name, shape, off in self.model.param_views()}
+        params = {}
+        for n, _ in self.model.named_parameters():
+            shape, off = views[n]
+            params[n] = self.ema[off:off + int(np.prod(shape))].view(tuple(shape)).cpu().clone()
+        return {"n_averaged": int(self.n_averaged.item()), "decay": float(self._ema_decay), "params": params}
+
+    def load_ema_checkpoint(self, d):
+        """Restore the average, the count and the decay from ema_checkpoint()'s dict, in place: a captured
+        graph stays valid, and its next replay continues from the loaded state."""
+        self._need_ema("load_ema_checkpoint()")
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep.load_ema_checkpoint() inside swap_ema()")
+        decay = check_ema_decay(d["decay"])
+        n_averaged = int(d["n_averaged"])
+        views = {name: (shape, off) for name, shape, off in self.model.param_views()}
+        names = [n for n, _ in self.model.named_parameters()]
+        missing = [n for n in names if n not in d["params"]]
+        if n_averaged < 0 or missing:
+            raise ValueError(f"TrainStep.load_ema_checkpoint: n_averaged {n_averaged}, missing parameters {missing}")
+        for n in names:
+            shape, off = views[n]
+            t = d["params"][n]
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"TrainStep.load_ema_checkpoint: {n} has shape {tuple(t.shape)}, not {tuple(shape)}")
+        for n in names:
+            shape, off = views[n]
+            self.ema[off:off + int(np.prod(shape))].view(tuple(shape)).copy_(d["params"][n])
+        self.n_averaged.fill_(n_averaged)
+        self._ema_write(decay)
+
     # -- accumulation (accum_iter > 1) ----------------------------------------------
     def _need_accum(self, what):
         if self.accum is None:
@@ -472,10 +620,14 @@ class TrainStep:
             self.sync.finish()
         elif self.fused_optimizer:
             self.backward_optimizer_step()
+            if self.ema is not None:
+                self.ema_update()
             return
         else:
             self.backward_phase(0)
         self.optimizer_step()
+        if self.ema is not None:
+            self.ema_update()
 
     def _accum_call(self, skel, sensor, label, update):
         """One micro-batch of an accumulating step; the all-reduce and the update on update calls only."""
@@ -493,6 +645,8 @@ class TrainStep:
             self.sync.all()
             if self.graph is None:
                 self.optimizer_step()
+                if self.ema is not None:
+                    self.ema_update()
             else:
                 if self._graph_legacy:
                     self._legacy_steps += 1
@@ -512,6 +666,9 @@ class TrainStep:
     def __call__(self, skel, sensor, label, update=None):
         """One batch. `update` (accumulating steps only): True / False decides whether this call ends
         with the optimizer update, instead of the reference's rule counted from begin_epoch()."""
+        if self._ema_swapped:
+            raise RuntimeError("TrainStep: called inside swap_ema(): the model holds the averaged weights, a step "
+                               "would train them")
         label = self.prepare(skel, sensor, label)
         if self.accum is not None:
             return self._accum_call(skel, sensor, label, update)
@@ -587,6 +744,8 @@ class TrainStep:
             check(lib().f3_optim_step_hyper(cfg, ptr(self.model.flat_parameters()), ptr(s0), ptr(s1), ptr(src),
                                             src.numel(), ptr(self.hyper), ptr(self.scalars), stream_handle()),
                   f"{self.kind} step")
+            if self.ema is not None:
+                self.ema_update()  # reads the count and the decay on replay
             if self.accum is not None:
                 self._accum_reset.fill_(1)
         self._hyper_key = key

@@ -22,6 +22,8 @@
  *   f3_segment_norms   <- param.grad.norm().item() per parameter   model/main.py:84-89
  *   f3_net_loss_ex     <- CrossEntropyLoss(label_smoothing=TRAIN.LABEL_SMOOTHING)   model/main.py:280
  *   f3_grad_accumulate <- .grad += g between the optimizer steps of TRAIN.ACCUM_ITER  model/main.py:115-132
+ *   f3_ema_update      <- AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay)).update_parameters(model)
+ *                         after optimizer.step() (torch.optim.swa_utils; the loop itself has no averaging)
  *
  * Conventions: plain pointers to device memory (HIP), sizes in elements, a HIP stream
  * passed as void*. No call allocates, frees or synchronises: every buffer (flat
@@ -355,6 +357,34 @@ int f3_net_loss_ex(f3_net* net, int batch, const float* out, const float* label,
  * acc and grads 16-byte aligned, reset_flag 4-byte aligned, else F3_EINVAL; so is n < 0. n = 0 only
  * clears the word. */
 int f3_grad_accumulate(float* acc, const float* grads, int64_t n, int* reset_flag, void* stream);
+
+/* ---- parameter EMA kept on the device ----
+ * f3_ema_update <- ema_model.update_parameters(model) after every optimizer.step(), with ema_model =
+ *                  torch.optim.swa_utils.AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay))
+ *                  and the default use_buffers=False (timm's ModelEma is the same recurrence), on one flat
+ *                  fp32 array.
+ * The EMA block: device memory of f3_ema_state_bytes() bytes (16), 8-byte aligned, zeroed by the caller:
+ *   byte 0  int64  n_averaged   updates so far
+ *   byte 8  fp64   decay
+ * The update reads both when it runs, so an update recorded into a HIP graph advances the count and
+ * follows a later f3_ema_set_decay on replay (the idea of the hyper block above). There is one form of the
+ * kernel, not a by-value form and a device-reading one. */
+int64_t f3_ema_state_bytes(void);
+/* Checks decay on the host (finite, in [0, 1]), then one one-thread launch on `stream` stores it into the
+ * block. To be called outside stream capture, ordered before the replay on the same stream, as
+ * f3_optim_hyper_set. F3_EINVAL (nothing launched, the block as it was): a bad decay, state NULL or not
+ * 8-byte aligned. */
+int f3_ema_set_decay(void* state, double decay, void* stream);
+/* n_averaged == 0: ema[i] = params[i], bit for bit (AveragedModel copies on its first update). Otherwise
+ *   ema[i] = (float)((double)ema[i] + (1.0 - decay) * ((double)params[i] - (double)ema[i]))
+ * evaluated in fp64 in exactly that order, without contraction, and rounded once (get_ema_multi_avg_fn's
+ * lerp(ema, p, 1 - decay); the fp64 convention of f3_optim_step). params is not written. n_averaged += 1
+ * happens after every element has been written: a second one-thread launch on the same stream, so no thread
+ * of the update reads a count that another has advanced. float4 body plus a scalar tail, grid-stride,
+ * 256-thread workgroups, at most 4096 of them. No atomics: the same inputs give the same bits on every run
+ * and every rank. F3_EINVAL, checked on the host before anything touches the device: a NULL pointer, ema or
+ * params not 16-byte aligned, state not 8-byte aligned, n < 0. n == 0 only advances the count. */
+int f3_ema_update(float* ema, const float* params, int64_t n, void* state, void* stream);
 
 /* Kernel-level entries used by the unit tests and bench.py: out[N,T_out,V,Cout] = conv_(KT,1)(x)
  * with x [N,T_in,V,Cin] channels-last, w in reference layout [Cout][Cin][KT], bias [Cout]
