@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "entry_table.h"
 #include "fall3.h"
 #include "kernels.h"
 #include "layers.h"
@@ -28,13 +29,6 @@ using namespace f3;
 using namespace f3::mu;
 
 namespace {
-
-struct Entry {
-  std::string name;
-  int kind;
-  std::vector<int64_t> shape;
-  int64_t off;
-};
 
 struct BnOff {
   int64_t w, b, rm, rv, nbt;
@@ -61,11 +55,9 @@ constexpr float kHeadDrop = 0.2f;   // Classification_Module Dropout(0.2)
 
 }  // namespace
 
-struct f3_musa {
+struct f3_musa : EntryTable {
   int V, T, C;
   int prec = F3_PRECISION_FP32;  // F3_PRECISION_BF16: the stream 1x1 convs on bf16 MFMA (fp32 accumulate)
-  std::vector<Entry> entries;
-  int64_t nparam = 0, nbuf = 0, ncnt = 0;
   StreamOff st[2];
   int64_t fc0_w, fc0_b, ln_w, ln_b, fc5_w, fc5_b;
   std::vector<BnOff*> bns;
@@ -73,24 +65,6 @@ struct f3_musa {
   unsigned seed = 0;
   int drop = 0;
   int trained_batch = 0;
-
-  int64_t add(const std::string& name, std::vector<int64_t> shape, int kind = F3_ENTRY_PARAM) {
-    int64_t n = 1;
-    for (auto d : shape) n *= d;
-    Entry e{name, kind, shape, 0};
-    if (kind == F3_ENTRY_PARAM) {
-      e.off = nparam;
-      nparam += (n + 3) / 4 * 4;
-    } else if (kind == F3_ENTRY_BUFFER) {
-      e.off = nbuf;
-      nbuf += n;
-    } else {
-      e.off = ncnt;
-      ncnt += 1;
-    }
-    entries.push_back(e);
-    return e.off;
-  }
   void add_bn(BnOff& o, const std::string& p, int C) {
     o.w = add(p + "weight", {C});
     o.b = add(p + "bias", {C});
@@ -655,14 +629,7 @@ int f3_musa_num_entries(const f3_musa* net) { return net ? (int)net->entries.siz
 
 int f3_musa_entry(const f3_musa* net, int i, const char** name, int* kind, int* ndim, int64_t* shape8,
                   int64_t* offset) {
-  if (!net || i < 0 || i >= (int)net->entries.size()) return F3_EINVAL;
-  const Entry& e = net->entries[i];
-  *name = e.name.c_str();
-  *kind = e.kind;
-  *ndim = (int)e.shape.size();
-  for (int d = 0; d < 8; ++d) shape8[d] = d < (int)e.shape.size() ? e.shape[d] : 0;
-  *offset = e.off;
-  return F3_OK;
+  return net ? net->get(i, name, kind, ndim, shape8, offset) : F3_EINVAL;
 }
 
 int64_t f3_musa_param_count(const f3_musa* net) { return net ? net->nparam : 0; }

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "entry_table.h"
 #include "fall3.h"
 #include "kernels.h"
 #include "layers.h"
@@ -27,13 +28,6 @@ using namespace f3;
 using namespace f3::sk;
 
 namespace {
-
-struct Entry {
-  std::string name;
-  int kind;
-  std::vector<int64_t> shape;
-  int64_t off;
-};
 
 struct AttnOff {
   int64_t table, wqkv, bqkv, wm, bm;
@@ -51,11 +45,9 @@ constexpr int NBLOCK = 6;
 
 }  // namespace
 
-struct f3_sktr {
+struct f3_sktr : EntryTable {
   int V, T, M, C;
   int prec = F3_PRECISION_FP32;  // F3_PRECISION_BF16: the block Linears on bf16 MFMA (fp32 accumulate)
-  std::vector<Entry> entries;
-  int64_t nparam = 0, nbuf = 0, ncnt = 0;
   int64_t e_w1 = 0, e_b1 = 0, e_w2 = 0, e_b2 = 0, fc_w = 0, fc_b = 0;
   BlockOff blk[NBLOCK];
   // the last training forward's randomness (backward replays it)
@@ -63,24 +55,6 @@ struct f3_sktr {
   unsigned seed = 0;
   float drop_p = 0.f;
   int trained_batch = 0;
-
-  int64_t add(const std::string& name, std::vector<int64_t> shape, int kind = F3_ENTRY_PARAM) {
-    int64_t n = 1;
-    for (auto d : shape) n *= d;
-    Entry e{name, kind, shape, 0};
-    if (kind == F3_ENTRY_PARAM) {
-      e.off = nparam;
-      nparam += (n + 3) / 4 * 4;  // 16-B aligned entries (float4 RMSprop)
-    } else if (kind == F3_ENTRY_BUFFER) {
-      e.off = nbuf;
-      nbuf += n;
-    } else {
-      e.off = ncnt;
-      ncnt += 1;
-    }
-    entries.push_back(e);
-    return e.off;
-  }
 };
 
 namespace {
@@ -278,14 +252,7 @@ int f3_sktr_num_entries(const f3_sktr* net) { return net ? (int)net->entries.siz
 
 int f3_sktr_entry(const f3_sktr* net, int i, const char** name, int* kind, int* ndim, int64_t* shape8,
                   int64_t* offset) {
-  if (!net || i < 0 || i >= (int)net->entries.size()) return F3_EINVAL;
-  const Entry& e = net->entries[i];
-  *name = e.name.c_str();
-  *kind = e.kind;
-  *ndim = (int)e.shape.size();
-  for (int d = 0; d < 8; ++d) shape8[d] = d < (int)e.shape.size() ? e.shape[d] : 0;
-  *offset = e.off;
-  return F3_OK;
+  return net ? net->get(i, name, kind, ndim, shape8, offset) : F3_EINVAL;
 }
 
 int64_t f3_sktr_param_count(const f3_sktr* net) { return net ? net->nparam : 0; }

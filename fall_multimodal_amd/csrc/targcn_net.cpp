@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "entry_table.h"
 #include "fall3.h"
 #include "kernels.h"
 #include "sensor.h"
@@ -27,13 +28,6 @@ using namespace f3;
 using namespace f3::tg;
 
 namespace {
-
-struct Entry {
-  std::string name;
-  int kind;
-  std::vector<int64_t> shape;
-  int64_t off;
-};
 
 struct EmbOff {
   int64_t pool, bpool, lin, linb;
@@ -48,10 +42,8 @@ constexpr int DIN0 = 3;
 
 }  // namespace
 
-struct f3_targcn {
+struct f3_targcn : EntryTable {
   int V, C, prec;
-  std::vector<Entry> entries;
-  int64_t nparam = 0, nbuf = 0;
   int64_t E = 0;
   EmbOff emb[2][2];  // [layer][gate, update]
   TaOff ta[2];
@@ -68,21 +60,6 @@ struct f3_targcn {
   ~f3_targcn() {
     for (auto& e : tev) if (e) (void)hipEventDestroy(e);
     for (auto& p : prof) if (p) (void)hipFree(p);
-  }
-
-  int64_t add(const std::string& name, std::vector<int64_t> shape, int kind = F3_ENTRY_PARAM) {
-    int64_t n = 1;
-    for (auto d : shape) n *= d;
-    Entry e{name, kind, shape, 0};
-    if (kind == F3_ENTRY_PARAM) {
-      e.off = nparam;
-      nparam += (n + 3) / 4 * 4;  // 16-B aligned entries (float4 RMSprop)
-    } else {
-      e.off = nbuf;
-      nbuf += n;
-    }
-    entries.push_back(e);
-    return e.off;
   }
 };
 
@@ -297,14 +274,7 @@ int f3_targcn_num_entries(const f3_targcn* net) { return net ? (int)net->entries
 
 int f3_targcn_entry(const f3_targcn* net, int i, const char** name, int* kind, int* ndim, int64_t* shape8,
                     int64_t* offset) {
-  if (!net || i < 0 || i >= (int)net->entries.size()) return F3_EINVAL;
-  const Entry& e = net->entries[i];
-  *name = e.name.c_str();
-  *kind = e.kind;
-  *ndim = (int)e.shape.size();
-  for (int d = 0; d < 8; ++d) shape8[d] = d < (int)e.shape.size() ? e.shape[d] : 0;
-  *offset = e.off;
-  return F3_OK;
+  return net ? net->get(i, name, kind, ndim, shape8, offset) : F3_EINVAL;
 }
 
 int64_t f3_targcn_param_count(const f3_targcn* net) { return net ? net->nparam : 0; }

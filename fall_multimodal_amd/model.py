@@ -20,7 +20,6 @@ fall3::net_backward (ops.py, torch.library, with fake kernels and autograd regis
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
 import sys
@@ -30,8 +29,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import ENTRY_BUFFER, ENTRY_COUNTER, ENTRY_PARAM, check, lib, ptr, require_device, stream_handle
+from . import _lib
+from ._flat import FlatModule, NativeHandle
+from ._lib import check, lib, ptr, require_device, stream_handle
 from .graph import STRATEGY_PARTITIONS, Graph
 
 MODEL_IDS = {"two_stgcan_bilstm": 0, "two_stgcan": 1, "stgcn": 2, "bilstm": 3}
@@ -82,11 +82,10 @@ class NetSpec:
     extra: dict = field(default_factory=dict)
 
 
-class NativeNet:
+class NativeNet(NativeHandle):
     """Owner of one f3_net handle and its state_dict table."""
 
     def __init__(self, spec: NetSpec, K: int, V: int):
-        L = lib()
         c = _lib.F3Config()
         c.model = MODEL_IDS[spec.model]
         c.num_node, c.num_partition, c.num_class = V, K, spec.num_class
@@ -103,34 +102,8 @@ class NativeNet:
             raise ValueError(f"precision must be one of {sorted(PRECISION_IDS)}, got {prec!r}")
         _log_precision_once(prec, spec.precision is None)
         c.precision = PRECISION_IDS[prec]
-        h = ctypes.c_void_p()
-        check(L.f3_net_create(ctypes.byref(c), ctypes.byref(h)), "f3_net_create")
-        self.h = h
-        self.entries = []
-        name, kind, nd = ctypes.c_char_p(), ctypes.c_int(), ctypes.c_int()
-        shape, off = (ctypes.c_int64 * 8)(), ctypes.c_int64()
-        for i in range(L.f3_net_num_entries(h)):
-            check(L.f3_net_entry(h, i, ctypes.byref(name), ctypes.byref(kind), ctypes.byref(nd), shape,
-                                 ctypes.byref(off)), "f3_net_entry")
-            self.entries.append((name.value.decode(), kind.value, tuple(shape[d] for d in range(nd.value)),
-                                 off.value))
+        super().__init__("net", c)
         self.precision = prec
-        self.nparam = L.f3_net_param_count(h)
-        self.nbuf = L.f3_net_buffer_count(h)
-        self.ncnt = L.f3_net_counter_count(h)
-        self._ws_bytes = {}
-
-    def workspace_bytes(self, batch):
-        if batch not in self._ws_bytes:
-            self._ws_bytes[batch] = int(lib().f3_net_workspace_bytes(self.h, batch))
-        return self._ws_bytes[batch]
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                lib().f3_net_destroy(self.h)
-        except Exception:
-            pass
 
 
 def _default_value(name, shape, A):
@@ -152,108 +125,32 @@ def _default_value(name, shape, A):
     return None
 
 
-class Fall3Net(nn.Module):
+class Fall3Net(FlatModule):
     """Generic native-backed module; the reference-named classes below configure it."""
 
     def __init__(self, spec: NetSpec, device=None):
         super().__init__()
         object.__setattr__(self, "spec", spec)
-        graph = Graph(spec.layout, spec.strategy)
-        A = graph.A
-        object.__setattr__(self, "_native", NativeNet(spec, A.shape[0], A.shape[1]))
-        object.__setattr__(self, "_op_id", ops.register(self))
+        A = Graph(spec.layout, spec.strategy).A
+        object.__setattr__(self, "_graph_A", A)
         object.__setattr__(self, "num_node", A.shape[1])
-        if device is None:
-            device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
-        dev = torch.device(device)
-        nat = self._native
-        flat_p = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
-        flat_b = torch.zeros(max(nat.nbuf, 1), dtype=torch.float32, device=dev)
-        flat_c = torch.zeros(max(nat.ncnt, 1), dtype=torch.int64, device=dev)
-        self._set_flats(flat_p, flat_b, flat_c)
-        shapes = {n: s for n, k, s, o in nat.entries}
-        with torch.no_grad():
-            for name, kind, shape, off in nat.entries:
-                t = self._view(kind, shape, off)
-                v = _default_value(name, shape, A)
-                if v is None:
-                    leaf = name.rsplit(".", 1)[-1]
-                    if len(shape) >= 2:          # Conv/Linear weight: kaiming_uniform(a=sqrt 5)
-                        fan_in = int(np.prod(shape[1:]))
-                    elif leaf == "weight":       # BatchNorm gamma
-                        t.fill_(1.0)
-                        fan_in = None
-                    else:                        # bias: U(+-1/sqrt(fan_in of its weight)); BN beta 0
-                        w = shapes.get(name[: -len("bias")] + "weight")
-                        fan_in = int(np.prod(w[1:])) if w is not None and len(w) >= 2 else None
-                        if fan_in is None:
-                            t.zero_()
-                    if fan_in:
-                        b = 1.0 / math.sqrt(fan_in)
-                        t.copy_(torch.empty(shape).uniform_(-b, b))
-                else:
-                    t.copy_(v)
-                self._register(name, kind, t)
+        self._build(NativeNet(spec, A.shape[0], A.shape[1]), spec.num_class, device)
 
-    # -- flat storage ----------------------------------------------------------
-    def _set_flats(self, p, b, c):
-        object.__setattr__(self, "_flat_params", p)
-        object.__setattr__(self, "_flat_buffers", b)
-        object.__setattr__(self, "_flat_counters", c)
-
-    def _view(self, kind, shape, off):
-        n = int(np.prod(shape)) if len(shape) else 1
-        flat = {ENTRY_PARAM: self._flat_params, ENTRY_BUFFER: self._flat_buffers,
-                ENTRY_COUNTER: self._flat_counters}[kind]
-        return flat[off:off + n].view(shape)
-
-    def _owner(self, name):
-        mod = self
-        *path, leaf = name.split(".")
-        for p in path:
-            if p not in mod._modules:
-                mod.add_module(p, nn.Module())
-            mod = mod._modules[p]
-        return mod, leaf
-
-    def _register(self, name, kind, t):
-        mod, leaf = self._owner(name)
-        if kind == ENTRY_PARAM:
-            mod.register_parameter(leaf, nn.Parameter(t))
-        else:
-            mod.register_buffer(leaf, t)
-
-    def _tensor(self, name):
-        mod, leaf = self._owner(name)
-        return mod._parameters[leaf] if leaf in mod._parameters else mod._buffers[leaf]
-
-    def _reflatten(self):
-        """Re-alias every parameter/buffer into fresh flat arrays (after .to()/.cuda())."""
-        nat = self._native
-        first = next(iter(self.parameters()))
-        dev = first.device
-        p = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
-        b = torch.zeros(max(nat.nbuf, 1), dtype=torch.float32, device=dev)
-        c = torch.zeros(max(nat.ncnt, 1), dtype=torch.int64, device=dev)
-        self._set_flats(p, b, c)
-        with torch.no_grad():
-            for name, kind, shape, off in nat.entries:
-                cur = self._tensor(name)
-                view = self._view(kind, shape, off)
-                view.copy_(cur.detach().to(view.dtype))
-                if kind == ENTRY_PARAM:
-                    cur.data = view
-                else:
-                    mod, leaf = self._owner(name)
-                    mod._buffers[leaf] = view
-
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn, recurse)
-        self._reflatten()
-        return self
-
-    def flat_parameters(self):
-        return self._flat_params
+    def _default(self, name, shape, shapes):
+        v = _default_value(name, shape, self._graph_A)
+        if v is not None:
+            return v
+        if len(shape) >= 2:          # Conv/Linear weight: kaiming_uniform(a=sqrt 5)
+            fan_in = int(np.prod(shape[1:]))
+        elif name.rsplit(".", 1)[-1] == "weight":  # BatchNorm gamma
+            return torch.ones(shape)
+        else:                        # bias: U(+-1/sqrt(fan_in of its weight)); BN beta 0
+            w = shapes.get(name[: -len("bias")] + "weight")
+            if w is None or len(w) < 2:
+                return torch.zeros(shape)
+            fan_in = int(np.prod(w[1:]))
+        b = 1.0 / math.sqrt(fan_in)
+        return torch.empty(shape).uniform_(-b, b)
 
     @property
     def precision(self):
@@ -265,9 +162,6 @@ class Fall3Net(nn.Module):
         the sensor branch's cooperative CNN1D group barrier timed out and wrote NaN into its outputs);
         wait=False checks only copies that have completed. The next forward / backward also raises."""
         check(lib().f3_net_status(self._native.h, 1 if wait else 0), "fall3 device status")
-
-    def param_views(self):
-        return [(name, shape, off) for name, kind, shape, off in self._native.entries if kind == ENTRY_PARAM]
 
     # -- forward ---------------------------------------------------------------
     def _inputs(self, args, kwargs):

@@ -24,10 +24,10 @@ import math
 
 import numpy as np
 import torch
-import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import ENTRY_BUFFER, ENTRY_PARAM, check, lib, ptr, require_device, stream_handle
+from . import _lib
+from ._flat import FlatModule, NativeHandle, _SideStep
+from ._lib import check, lib, ptr, require_device, stream_handle
 
 
 class adjGraph:  # noqa: N801  (reference name)
@@ -49,41 +49,14 @@ class adjGraph:  # noqa: N801  (reference name)
         self.A = (A @ Dn)[None]
 
 
-class _NativeMusa:
+class _NativeMusa(NativeHandle):
     def __init__(self, V, T, num_class, precision=0):
-        L = lib()
         c = _lib.F3MusaConfig()
         c.num_point, c.frames, c.num_class, c.precision = V, T, num_class, precision
-        h = ctypes.c_void_p()
-        check(L.f3_musa_create(ctypes.byref(c), ctypes.byref(h)), "f3_musa_create")
-        self.h = h
-        self.entries = []
-        name, kind, nd = ctypes.c_char_p(), ctypes.c_int(), ctypes.c_int()
-        shape, off = (ctypes.c_int64 * 8)(), ctypes.c_int64()
-        for i in range(L.f3_musa_num_entries(h)):
-            check(L.f3_musa_entry(h, i, ctypes.byref(name), ctypes.byref(kind), ctypes.byref(nd), shape,
-                                  ctypes.byref(off)), "f3_musa_entry")
-            self.entries.append((name.value.decode(), kind.value, tuple(shape[d] for d in range(nd.value)),
-                                 off.value))
-        self.nparam = L.f3_musa_param_count(h)
-        self.nbuf = L.f3_musa_buffer_count(h)
-        self.ncnt = L.f3_musa_counter_count(h)
-        self._ws = {}
-
-    def workspace_bytes(self, batch):
-        if batch not in self._ws:
-            self._ws[batch] = int(lib().f3_musa_workspace_bytes(self.h, batch))
-        return self._ws[batch]
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                lib().f3_musa_destroy(self.h)
-        except Exception:
-            pass
+        super().__init__("musa", c)
 
 
-class Model(nn.Module):
+class Model(FlatModule):
     """musa_model.Model on the MI355X path (the driver's configuration)."""
 
     def __init__(self, num_class, num_point, max_frame, graph, bias, edge, block_size, embed_dim=64, n_stage=1,
@@ -106,28 +79,17 @@ class Model(nn.Module):
         object.__setattr__(self, "frames", frames)
         object.__setattr__(self, "dropblock", bool(dropblock))
         object.__setattr__(self, "_gen", torch.Generator().manual_seed(int(seed)))
-        object.__setattr__(self, "_native", _NativeMusa(num_point, frames, num_class, 1 if precision == "bf16" else 0))
-        object.__setattr__(self, "_op_id", ops.register(self))
-        if device is None:
-            device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
-        self._alloc(torch.device(device))
-        shapes = {n: s for n, k, s, o in self._native.entries}
-        with torch.no_grad():
-            for name, kind, shape, off in self._native.entries:
-                t = self._view(kind, shape, off)
-                t.copy_(torch.from_numpy(A) if name.endswith(".A") else self._default(name, shape, shapes))
-                self._register(name, kind, t)
+        object.__setattr__(self, "_graph_A", A)
+        self._build(_NativeMusa(num_point, frames, num_class, 1 if precision == "bf16" else 0), num_class, device)
 
-    def _alloc(self, dev):
-        nat = self._native
-        object.__setattr__(self, "_flat_params", torch.zeros(nat.nparam, dtype=torch.float32, device=dev))
-        object.__setattr__(self, "_flat_buffers", torch.zeros(max(nat.nbuf, 1), dtype=torch.float32, device=dev))
-        object.__setattr__(self, "_counters", torch.zeros(max(nat.ncnt, 1), dtype=torch.int64, device=dev))
+    def _requires_grad(self, name):
+        return not name.endswith(".A")  # the reference registers A as a frozen Parameter
 
-    @staticmethod
-    def _default(name, shape, shapes):
-        """PyTorch default inits (init_param at musa_model.py:408-420 is never called)."""
+    def _default(self, name, shape, shapes):
+        """The graph for A, else PyTorch default inits (init_param at musa_model.py:408-420 is never called)."""
         leaf = name.rsplit(".", 1)[-1]
+        if leaf == "A":
+            return torch.from_numpy(self._graph_A)
         if leaf == "edge":
             return torch.ones(shape)
         if leaf == "running_mean":
@@ -147,52 +109,6 @@ class Model(nn.Module):
             fan_in = int(np.prod(shape[1:]))
         b = 1.0 / math.sqrt(fan_in)
         return torch.empty(shape).uniform_(-b, b)
-
-    def _view(self, kind, shape, off):
-        n = int(np.prod(shape)) if len(shape) else 1
-        if kind == ENTRY_PARAM:
-            return self._flat_params[off:off + n].view(shape)
-        if kind == ENTRY_BUFFER:
-            return self._flat_buffers[off:off + n].view(shape)
-        return self._counters[off:off + 1].view(shape)
-
-    def _owner(self, name):
-        mod = self
-        *path, leaf = name.split(".")
-        for p in path:
-            if p not in mod._modules:
-                mod.add_module(p, nn.Module())
-            mod = mod._modules[p]
-        return mod, leaf
-
-    def _register(self, name, kind, t):
-        mod, leaf = self._owner(name)
-        if kind == ENTRY_PARAM:
-            mod.register_parameter(leaf, nn.Parameter(t, requires_grad=not name.endswith(".A")))
-        else:
-            mod.register_buffer(leaf, t)
-
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn, recurse)
-        dev = next(iter(self.parameters())).device
-        self._alloc(dev)
-        with torch.no_grad():
-            for name, kind, shape, off in self._native.entries:
-                mod, leaf = self._owner(name)
-                cur = mod._parameters[leaf] if leaf in mod._parameters else mod._buffers[leaf]
-                view = self._view(kind, shape, off)
-                view.copy_(cur.detach())
-                if kind == ENTRY_PARAM:
-                    cur.data = view
-                else:
-                    mod._buffers[leaf] = view
-        return self
-
-    def flat_parameters(self):
-        return self._flat_params
-
-    def param_views(self):
-        return [(name, shape, off) for name, kind, shape, off in self._native.entries if kind == ENTRY_PARAM]
 
     def check_inputs(self, x):
         require_device(x, "x")
@@ -250,47 +166,22 @@ def grad_is_none(name, dropblock_active):
     return bool(_SEP_EDGE.search(name)) and not dropblock_active
 
 
-class MusaStep:
+class MusaStep(_SideStep):
     """Fused musa_model training step: forward -> soft-target CE -> backward -> RMSprop on one HIP
     stream with preallocated buffers (main.py's train loop body with RMSprop(lr=1e-3))."""
 
     def __init__(self, model: Model, batch, lr=1e-3, alpha=0.99, eps=1e-8):
-        self.model, self.N = model, batch
-        self.lr, self.alpha, self.eps = lr, alpha, eps
-        dev = model.flat_parameters().device
-        nat = model._native
-        self.grads = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
-        self.square_avg = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
-        self.ws = torch.empty(nat.workspace_bytes(batch), dtype=torch.uint8, device=dev)
-        self.out = torch.empty(batch, model.num_classes, dtype=torch.float32, device=dev)
-        self.dout = torch.empty_like(self.out)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        super().__init__(model, batch, lr, alpha, eps)
         self.last_seed = None
+
+    def _grad_is_none(self, name):
         # A (frozen) has no gradient; the SepTemporal blocks' edges get the zero gradient the
         # reference's DropBlock gives them (None without DropBlock). RMSprop maps a zero gradient
         # to a zero update (square_avg stays 0), as torch.optim.RMSprop (no weight decay) does
-        for (name, shape, off), p in zip(model.param_views(), model.parameters()):
-            if not grad_is_none(name, model.dropblock):
-                p.grad = self.grads[off:off + int(np.prod(shape))].view(shape)
+        return grad_is_none(name, self.model.dropblock)
 
     def forward_backward(self, x, label, seed=None):
-        m = self.model
-        m.check_inputs(x)
-        if x.shape[0] != self.N or not x.is_contiguous() or x.dtype != torch.float32:
-            raise ValueError(f"MusaStep: x must be contiguous fp32 with batch {self.N}")
-        if tuple(label.shape) != (self.N, m.num_classes) or label.dtype != torch.float32 or not label.is_contiguous():
-            raise ValueError(f"MusaStep: label must be contiguous fp32 [{self.N},{m.num_classes}]")
-        seed = m.draw_seed() if seed is None else int(seed)
+        self._check(x, label)
+        seed = self.model.draw_seed() if seed is None else int(seed)
         self.last_seed = seed
-        st = stream_handle()
-        m.native_forward(x, self.out, self.ws, True, seed, stream=st)
-        check(lib().f3_soft_ce(ptr(self.out), ptr(label), self.N, m.num_classes, ptr(self.loss), ptr(self.dout), st),
-              "soft ce")
-        m.native_backward(self.N, self.dout, self.grads, self.ws, st)
-
-    def __call__(self, x, label, seed=None):
-        self.forward_backward(x, label, seed)
-        check(lib().f3_rmsprop_step(ptr(self.model.flat_parameters()), ptr(self.square_avg), ptr(self.grads),
-                                    self.grads.numel(), self.lr, self.alpha, self.eps, 1.0, stream_handle()),
-              "rmsprop")
-        return self.loss
+        self._run(x, label, True, seed)

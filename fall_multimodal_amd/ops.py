@@ -60,43 +60,35 @@ def _module(net: int):
 
 
 # ---------------------------------------------------------------------------------------------
-# 3-stream / 2-stream / single-stream / sensor models (f3_net)
+# bodies the four models' ops share
 # ---------------------------------------------------------------------------------------------
-@torch.library.custom_op("fall3::net_forward", mutates_args=())
-def net_forward(net: int, params: List[Tensor], buffers: Tensor, counters: Tensor, skel: Optional[Tensor],
-                sensor: Optional[Tensor], training: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
-    """Functional: returns (out, workspace, new running buffers, new counters); the module copies the
-    new BatchNorm running statistics back (a mutating op could not carry an autograd formula)."""
-    m = _module(net)
-    ref = skel if skel is not None else sensor
+def _out_ws(m, ref):
+    """(logits, workspace) for the batch of `ref`, on its device."""
     N = ref.shape[0]
-    ws = torch.empty(m._native.workspace_bytes(N), dtype=torch.uint8, device=ref.device)
-    out = torch.empty(N, m.spec.num_class, dtype=torch.float32, device=ref.device)
-    nb, nc = buffers.clone(), counters.clone()
-    m.native_forward(skel, sensor, out, ws, training, buffers=nb, counters=nc)
-    return out, ws, nb, nc
+    return (torch.empty(N, m.n_class, dtype=torch.float32, device=ref.device),
+            torch.empty(m._native.workspace_bytes(N), dtype=torch.uint8, device=ref.device))
 
 
-@net_forward.register_fake
-def _(net, params, buffers, counters, skel, sensor, training):
-    m = _module(net)
-    ref = skel if skel is not None else sensor
+def _fake_out_ws(m, ref):
     N = ref.shape[0]
-    return (ref.new_empty(N, m.spec.num_class, dtype=torch.float32),
-            ref.new_empty(m._native.workspace_bytes(N), dtype=torch.uint8), torch.empty_like(buffers),
-            torch.empty_like(counters))
+    return (ref.new_empty(N, m.n_class, dtype=torch.float32),
+            ref.new_empty(m._native.workspace_bytes(N), dtype=torch.uint8))
 
 
-@torch.library.custom_op("fall3::net_backward", mutates_args=())
-def net_backward(net: int, params: List[Tensor], dout: Tensor, workspace: Tensor) -> Tensor:
+def _clone_state(buffers, counters):
+    """The copies a functional forward updates in place of the module's running statistics / counters."""
+    return buffers.clone(), counters.clone()
+
+
+def _flat_backward(net, dout, workspace):
+    """The model's native backward into a fresh flat gradient (params layout)."""
     m = _module(net)
     grads = torch.empty(m._native.nparam, dtype=torch.float32, device=dout.device)
     m.native_backward(dout.shape[0], dout.contiguous(), grads, workspace)
     return grads
 
 
-@net_backward.register_fake
-def _(net, params, dout, workspace):
+def _fake_flat_backward(net, dout):
     return dout.new_empty(_module(net)._native.nparam, dtype=torch.float32)
 
 
@@ -107,13 +99,6 @@ def _no_grad_outputs(ctx, output):
     trace of the unchanged main.py loop)."""
     ctx.set_materialize_grads(False)
     ctx.mark_non_differentiable(*output[1:])
-
-
-def _net_setup(ctx, inputs, output):
-    net, params, buffers, counters, skel, sensor, training = inputs
-    ctx.net, ctx.training = net, training
-    ctx.save_for_backward(output[1])
-    _no_grad_outputs(ctx, output)
 
 
 def _split_grads(m, grads):
@@ -134,13 +119,55 @@ def _split_grads(m, grads):
     return [grads.as_strided(shape, stride, o0 + off) for shape, stride, off in table]
 
 
-def _net_backward(ctx, dout, dws, dbuf, dcnt):
+def _training_backward(ctx, dout, backward_op):
+    """Parameter gradients of a forward that saved its workspace (training mode only)."""
     if not ctx.training:
         raise RuntimeError("fall3: backward through an eval-mode forward is not supported")
     (ws,) = ctx.saved_tensors
     m = _module(ctx.net)
-    grads = torch.ops.fall3.net_backward(ctx.net, list(m.parameters()), dout.float(), ws)
-    return None, _split_grads(m, grads), None, None, None, None, None
+    return m, _split_grads(m, backward_op(ctx.net, list(m.parameters()), dout.float(), ws))
+
+
+# ---------------------------------------------------------------------------------------------
+# 3-stream / 2-stream / single-stream / sensor models (f3_net)
+# ---------------------------------------------------------------------------------------------
+@torch.library.custom_op("fall3::net_forward", mutates_args=())
+def net_forward(net: int, params: List[Tensor], buffers: Tensor, counters: Tensor, skel: Optional[Tensor],
+                sensor: Optional[Tensor], training: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """Functional: returns (out, workspace, new running buffers, new counters); the module copies the
+    new BatchNorm running statistics back (a mutating op could not carry an autograd formula)."""
+    m = _module(net)
+    out, ws = _out_ws(m, skel if skel is not None else sensor)
+    nb, nc = _clone_state(buffers, counters)
+    m.native_forward(skel, sensor, out, ws, training, buffers=nb, counters=nc)
+    return out, ws, nb, nc
+
+
+@net_forward.register_fake
+def _(net, params, buffers, counters, skel, sensor, training):
+    return (*_fake_out_ws(_module(net), skel if skel is not None else sensor), torch.empty_like(buffers),
+            torch.empty_like(counters))
+
+
+@torch.library.custom_op("fall3::net_backward", mutates_args=())
+def net_backward(net: int, params: List[Tensor], dout: Tensor, workspace: Tensor) -> Tensor:
+    return _flat_backward(net, dout, workspace)
+
+
+@net_backward.register_fake
+def _(net, params, dout, workspace):
+    return _fake_flat_backward(net, dout)
+
+
+def _net_setup(ctx, inputs, output):
+    ctx.net, ctx.training = inputs[0], inputs[6]
+    ctx.save_for_backward(output[1])
+    _no_grad_outputs(ctx, output)
+
+
+def _net_backward(ctx, dout, dws, dbuf, dcnt):
+    _, gl = _training_backward(ctx, dout, torch.ops.fall3.net_backward)
+    return None, gl, None, None, None, None, None
 
 
 net_forward.register_autograd(_net_backward, setup_context=_net_setup)
@@ -152,32 +179,24 @@ net_forward.register_autograd(_net_backward, setup_context=_net_setup)
 @torch.library.custom_op("fall3::targcn_forward", mutates_args=())
 def targcn_forward(net: int, params: List[Tensor], buffers: Tensor, source: Tensor) -> Tuple[Tensor, Tensor]:
     m = _module(net)
-    N = source.shape[0]
-    ws = torch.empty(m._native.workspace_bytes(N), dtype=torch.uint8, device=source.device)
-    out = torch.empty(N, m.num_class, dtype=torch.float32, device=source.device)
+    out, ws = _out_ws(m, source)
     m.native_forward(source, out, ws)
     return out, ws
 
 
 @targcn_forward.register_fake
 def _(net, params, buffers, source):
-    m = _module(net)
-    N = source.shape[0]
-    return (source.new_empty(N, m.num_class, dtype=torch.float32),
-            source.new_empty(m._native.workspace_bytes(N), dtype=torch.uint8))
+    return _fake_out_ws(_module(net), source)
 
 
 @torch.library.custom_op("fall3::targcn_backward", mutates_args=())
 def targcn_backward(net: int, params: List[Tensor], buffers: Tensor, dout: Tensor, workspace: Tensor) -> Tensor:
-    m = _module(net)
-    grads = torch.empty(m._native.nparam, dtype=torch.float32, device=dout.device)
-    m.native_backward(dout.shape[0], dout.contiguous(), grads, workspace)
-    return grads
+    return _flat_backward(net, dout, workspace)
 
 
 @targcn_backward.register_fake
 def _(net, params, buffers, dout, workspace):
-    return dout.new_empty(_module(net)._native.nparam, dtype=torch.float32)
+    return _fake_flat_backward(net, dout)
 
 
 def _tg_setup(ctx, inputs, output):
@@ -204,34 +223,25 @@ def sktr_forward(net: int, params: List[Tensor], buffers: Tensor, counters: Tens
                  sd: List[float], seed: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """Functional like net_forward: returns the new BatchNorm3d running statistics / counters."""
     m = _module(net)
-    N = x.shape[0]
-    ws = torch.empty(m._native.workspace_bytes(N), dtype=torch.uint8, device=x.device)
-    out = torch.empty(N, m.num_classes, dtype=torch.float32, device=x.device)
-    nb, nc = buffers.clone(), counters.clone()
+    out, ws = _out_ws(m, x)
+    nb, nc = _clone_state(buffers, counters)
     m.native_forward(x, out, ws, training, sd, seed, buffers=nb, counters=nc)
     return out, ws, nb, nc
 
 
 @sktr_forward.register_fake
 def _(net, params, buffers, counters, x, training, sd, seed):
-    m = _module(net)
-    N = x.shape[0]
-    return (x.new_empty(N, m.num_classes, dtype=torch.float32),
-            x.new_empty(m._native.workspace_bytes(N), dtype=torch.uint8), torch.empty_like(buffers),
-            torch.empty_like(counters))
+    return (*_fake_out_ws(_module(net), x), torch.empty_like(buffers), torch.empty_like(counters))
 
 
 @torch.library.custom_op("fall3::sktr_backward", mutates_args=())
 def sktr_backward(net: int, params: List[Tensor], dout: Tensor, workspace: Tensor) -> Tensor:
-    m = _module(net)
-    grads = torch.empty(m._native.nparam, dtype=torch.float32, device=dout.device)
-    m.native_backward(dout.shape[0], dout.contiguous(), grads, workspace)
-    return grads
+    return _flat_backward(net, dout, workspace)
 
 
 @sktr_backward.register_fake
 def _(net, params, dout, workspace):
-    return dout.new_empty(_module(net)._native.nparam, dtype=torch.float32)
+    return _fake_flat_backward(net, dout)
 
 
 def _sk_setup(ctx, inputs, output):
@@ -241,12 +251,8 @@ def _sk_setup(ctx, inputs, output):
 
 
 def _sk_backward(ctx, dout, dws, dbuf, dcnt):
-    if not ctx.training:
-        raise RuntimeError("fall3: backward through an eval-mode forward is not supported")
-    (ws,) = ctx.saved_tensors
-    m = _module(ctx.net)
-    grads = torch.ops.fall3.sktr_backward(ctx.net, list(m.parameters()), dout.float(), ws)
-    return None, _split_grads(m, grads), None, None, None, None, None, None
+    _, gl = _training_backward(ctx, dout, torch.ops.fall3.sktr_backward)
+    return None, gl, None, None, None, None, None, None
 
 
 sktr_forward.register_autograd(_sk_backward, setup_context=_sk_setup)
@@ -259,46 +265,33 @@ sktr_forward.register_autograd(_sk_backward, setup_context=_sk_setup)
 def musa_forward(net: int, params: List[Tensor], buffers: Tensor, counters: Tensor, x: Tensor, training: bool,
                  seed: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     m = _module(net)
-    N = x.shape[0]
-    ws = torch.empty(m._native.workspace_bytes(N), dtype=torch.uint8, device=x.device)
-    out = torch.empty(N, m.num_classes, dtype=torch.float32, device=x.device)
-    nb, nc = buffers.clone(), counters.clone()
+    out, ws = _out_ws(m, x)
+    nb, nc = _clone_state(buffers, counters)
     m.native_forward(x, out, ws, training, seed, buffers=nb, counters=nc)
     return out, ws, nb, nc
 
 
 @musa_forward.register_fake
 def _(net, params, buffers, counters, x, training, seed):
-    m = _module(net)
-    N = x.shape[0]
-    return (x.new_empty(N, m.num_classes, dtype=torch.float32),
-            x.new_empty(m._native.workspace_bytes(N), dtype=torch.uint8), torch.empty_like(buffers),
-            torch.empty_like(counters))
+    return (*_fake_out_ws(_module(net), x), torch.empty_like(buffers), torch.empty_like(counters))
 
 
 @torch.library.custom_op("fall3::musa_backward", mutates_args=())
 def musa_backward(net: int, params: List[Tensor], dout: Tensor, workspace: Tensor) -> Tensor:
-    m = _module(net)
-    grads = torch.empty(m._native.nparam, dtype=torch.float32, device=dout.device)
-    m.native_backward(dout.shape[0], dout.contiguous(), grads, workspace)
-    return grads
+    return _flat_backward(net, dout, workspace)
 
 
 @musa_backward.register_fake
 def _(net, params, dout, workspace):
-    return dout.new_empty(_module(net)._native.nparam, dtype=torch.float32)
+    return _fake_flat_backward(net, dout)
 
 
 def _mu_backward(ctx, dout, dws, dbuf, dcnt):
-    if not ctx.training:
-        raise RuntimeError("fall3: backward through an eval-mode forward is not supported")
-    (ws,) = ctx.saved_tensors
-    m = _module(ctx.net)
-    grads = torch.ops.fall3.musa_backward(ctx.net, list(m.parameters()), dout.float(), ws)
+    m, gl = _training_backward(ctx, dout, torch.ops.fall3.musa_backward)
     from .musa import grad_is_none
     # None where the reference's autograd leaves None: A (frozen) always, the SepTemporal edges
     # unless DropBlock ran (then the reference gives them a zero tensor; musa.grad_is_none)
-    gl = [None if grad_is_none(name, m.dropblock) else g for g, (name, _, _) in zip(_split_grads(m, grads), m.param_views())]
+    gl = [None if grad_is_none(name, m.dropblock) else g for g, (name, _, _) in zip(gl, m.param_views())]
     return None, gl, None, None, None, None, None
 
 

@@ -27,48 +27,22 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, ops
-from ._lib import ENTRY_BUFFER, ENTRY_COUNTER, ENTRY_PARAM, check, lib, ptr, require_device, stream_handle
+from . import _lib
+from ._flat import FlatModule, NativeHandle, _SideStep
+from ._lib import check, lib, ptr, require_device, stream_handle
 
 NBLOCK = 6
 SD_RATES = np.linspace(0, 0.5, NBLOCK)  # skeleton_transformer.py:380
 
 
-class _NativeSktr:
+class _NativeSktr(NativeHandle):
     def __init__(self, V, T, M, num_class, precision=0):
-        L = lib()
         c = _lib.F3SktrConfig()
         c.num_joint, c.frames, c.persons, c.num_class, c.precision = V, T, M, num_class, precision
-        h = ctypes.c_void_p()
-        check(L.f3_sktr_create(ctypes.byref(c), ctypes.byref(h)), "f3_sktr_create")
-        self.h = h
-        self.entries = []
-        name, kind, nd = ctypes.c_char_p(), ctypes.c_int(), ctypes.c_int()
-        shape, off = (ctypes.c_int64 * 8)(), ctypes.c_int64()
-        for i in range(L.f3_sktr_num_entries(h)):
-            check(L.f3_sktr_entry(h, i, ctypes.byref(name), ctypes.byref(kind), ctypes.byref(nd), shape,
-                                  ctypes.byref(off)), "f3_sktr_entry")
-            self.entries.append((name.value.decode(), kind.value, tuple(shape[d] for d in range(nd.value)),
-                                 off.value))
-        self.nparam = L.f3_sktr_param_count(h)
-        self.nbuf = L.f3_sktr_buffer_count(h)
-        self.ncnt = L.f3_sktr_counter_count(h)
-        self._ws = {}
-
-    def workspace_bytes(self, batch):
-        if batch not in self._ws:
-            self._ws[batch] = int(lib().f3_sktr_workspace_bytes(self.h, batch))
-        return self._ws[batch]
-
-    def __del__(self):
-        try:
-            if getattr(self, "h", None):
-                lib().f3_sktr_destroy(self.h)
-        except Exception:
-            pass
+        super().__init__("sktr", c)
 
 
-class SkeletonTransformer(nn.Module):
+class SkeletonTransformer(FlatModule):
     """skeleton_transformer.py:360-435 on the MI355X path."""
 
     def __init__(self, in_channels: int = 3, n_joints: int = 14, seq_len: int = 30, num_classes: int = 11,
@@ -92,24 +66,8 @@ class SkeletonTransformer(nn.Module):
         object.__setattr__(self, "dropout_p", float(dropout_p))
         object.__setattr__(self, "stochastic_depth", bool(stochastic_depth))
         object.__setattr__(self, "_gen", torch.Generator().manual_seed(int(seed)))
-        object.__setattr__(self, "_native", _NativeSktr(n_joints, seq_len, persons, num_classes,
-                                                        1 if precision == "bf16" else 0))
-        object.__setattr__(self, "_op_id", ops.register(self))
-        if device is None:
-            device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
-        self._alloc(torch.device(device))
-        shapes = {n: s for n, k, s, o in self._native.entries}
-        with torch.no_grad():
-            for name, kind, shape, off in self._native.entries:
-                t = self._view(kind, shape, off)
-                t.copy_(self._default(name, shape, shapes))
-                self._register(name, kind, t)
-
-    def _alloc(self, dev):
-        nat = self._native
-        object.__setattr__(self, "_flat_params", torch.zeros(nat.nparam, dtype=torch.float32, device=dev))
-        object.__setattr__(self, "_flat_buffers", torch.zeros(max(nat.nbuf, 1), dtype=torch.float32, device=dev))
-        object.__setattr__(self, "_counters", torch.zeros(max(nat.ncnt, 1), dtype=torch.int64, device=dev))
+        self._build(_NativeSktr(n_joints, seq_len, persons, num_classes, 1 if precision == "bf16" else 0),
+                    num_classes, device)
 
     @staticmethod
     def _default(name, shape, shapes):
@@ -132,52 +90,6 @@ class SkeletonTransformer(nn.Module):
             fan_in = int(np.prod(shape[1:]))
         b = 1.0 / math.sqrt(fan_in)
         return torch.empty(shape).uniform_(-b, b)
-
-    def _view(self, kind, shape, off):
-        n = int(np.prod(shape)) if len(shape) else 1
-        if kind == ENTRY_PARAM:
-            return self._flat_params[off:off + n].view(shape)
-        if kind == ENTRY_BUFFER:
-            return self._flat_buffers[off:off + n].view(shape)
-        return self._counters[off:off + 1].view(shape)
-
-    def _owner(self, name):
-        mod = self
-        *path, leaf = name.split(".")
-        for p in path:
-            if p not in mod._modules:
-                mod.add_module(p, nn.Module())
-            mod = mod._modules[p]
-        return mod, leaf
-
-    def _register(self, name, kind, t):
-        mod, leaf = self._owner(name)
-        if kind == ENTRY_PARAM:
-            mod.register_parameter(leaf, nn.Parameter(t))
-        else:
-            mod.register_buffer(leaf, t)
-
-    def _apply(self, fn, recurse=True):
-        super()._apply(fn, recurse)
-        dev = next(iter(self.parameters())).device
-        self._alloc(dev)
-        with torch.no_grad():
-            for name, kind, shape, off in self._native.entries:
-                mod, leaf = self._owner(name)
-                cur = mod._parameters[leaf] if leaf in mod._parameters else mod._buffers[leaf]
-                view = self._view(kind, shape, off)
-                view.copy_(cur.detach())
-                if kind == ENTRY_PARAM:
-                    cur.data = view
-                else:
-                    mod._buffers[leaf] = view
-        return self
-
-    def flat_parameters(self):
-        return self._flat_params
-
-    def param_views(self):
-        return [(name, shape, off) for name, kind, shape, off in self._native.entries if kind == ENTRY_PARAM]
 
     def check_inputs(self, x):
         require_device(x, "x")
@@ -232,50 +144,19 @@ class SkeletonTransformer(nn.Module):
         return out
 
 
-class SktrStep:
+class SktrStep(_SideStep):
     """Fused SkeletonTransformer training step: forward -> soft-target CE -> backward -> RMSprop on
     one HIP stream, every buffer preallocated (the CV notebook's loop body for one fold)."""
 
     def __init__(self, model: SkeletonTransformer, batch, lr=1e-3, alpha=0.99, eps=1e-8):
-        self.model, self.N = model, batch
-        self.lr, self.alpha, self.eps = lr, alpha, eps
-        dev = model.flat_parameters().device
-        nat = model._native
-        self.grads = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
-        self.square_avg = torch.zeros(nat.nparam, dtype=torch.float32, device=dev)
-        self.ws = torch.empty(nat.workspace_bytes(batch), dtype=torch.uint8, device=dev)
-        self.out = torch.empty(batch, model.num_classes, dtype=torch.float32, device=dev)
-        self.dout = torch.empty_like(self.out)
-        self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        super().__init__(model, batch, lr, alpha, eps)
         self.last_draws = None
-        for (name, shape, off), p in zip(model.param_views(), model.parameters()):
-            p.grad = self.grads[off:off + int(np.prod(shape))].view(shape)
-
-    def _check(self, x, label):
-        self.model.check_inputs(x)
-        if x.shape[0] != self.N or not x.is_contiguous() or x.dtype != torch.float32:
-            raise ValueError(f"SktrStep: x must be contiguous fp32 with batch {self.N}")
-        if tuple(label.shape) != (self.N, self.model.num_classes) or label.dtype != torch.float32 \
-                or not label.is_contiguous() or label.device != x.device:
-            raise ValueError(f"SktrStep: label must be contiguous fp32 [{self.N},{self.model.num_classes}] on the device")
 
     def forward_backward(self, x, label, sd=None, seed=None):
         self._check(x, label)
-        m = self.model
         if sd is None or seed is None:
-            dsd, dseed = m.draw_randomness()
+            dsd, dseed = self.model.draw_randomness()
             sd = dsd if sd is None else sd
             seed = dseed if seed is None else seed
         self.last_draws = (list(sd), int(seed))
-        st = stream_handle()
-        m.native_forward(x, self.out, self.ws, True, sd, seed, stream=st)
-        check(lib().f3_soft_ce(ptr(self.out), ptr(label), self.N, m.num_classes, ptr(self.loss), ptr(self.dout), st),
-              "soft ce")
-        m.native_backward(self.N, self.dout, self.grads, self.ws, st)
-
-    def __call__(self, x, label, sd=None, seed=None):
-        self.forward_backward(x, label, sd, seed)
-        check(lib().f3_rmsprop_step(ptr(self.model.flat_parameters()), ptr(self.square_avg), ptr(self.grads),
-                                    self.grads.numel(), self.lr, self.alpha, self.eps, 1.0, stream_handle()),
-              "rmsprop")
-        return self.loss
+        self._run(x, label, True, sd, seed)

@@ -26,6 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import metrics as _metrics, ops, optim as _optim
+from ._flat import grad_views
 from ._lib import ENTRY_PARAM, check, lib, ptr, stream_handle
 
 
@@ -295,8 +296,7 @@ class TrainStep:
         if self.accum is not None:
             self.phased = False
         # expose the flat gradient through the usual .grad attributes
-        for (name, shape, off), p in zip(model.param_views(), model.parameters()):
-            p.grad = self._gsrc[off:off + int(np.prod(shape))].view(shape)
+        grad_views(model, self._gsrc)
         self.graph = None
         self._static = None
         # world 1: the RMSprop update per layer inside the backward (F3_FUSED_OPT=0: one launch after it)

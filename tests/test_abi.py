@@ -193,6 +193,12 @@ def test_custom_ops_registered_with_fake_kernels():
                                                       torch.empty(6, 3, 30, 14, 1), True, [1.0] * 18, 7)
         assert tuple(o3.shape) == (6, 11) and w3.numel() == k._native.workspace_bytes(6)
         assert torch.ops.fall3.sktr_backward(k._op_id, list(k.parameters()), o3, w3).numel() == k._native.nparam
+        u = f3.musa.Model(11, 14, 300, f3.musa.adjGraph("coco_cut", "uniform"), True, True, 41, device="cpu")
+        o4, w4, b4, c4 = torch.ops.fall3.musa_forward(u._op_id, list(u.parameters()), u._flat_buffers, u._counters,
+                                                      torch.empty(5, 3, 30, 14), True, 7)
+        assert tuple(o4.shape) == (5, 11) and w4.numel() == u._native.workspace_bytes(5)
+        assert b4.shape == u._flat_buffers.shape and c4.shape == u._counters.shape and c4.dtype == torch.int64
+        assert torch.ops.fall3.musa_backward(u._op_id, list(u.parameters()), o4, w4).numel() == u._native.nparam
 
 
 @pytest.mark.parametrize("V,T,M", [(14, 30, 1), (17, 30, 2), (18, 32, 1)])
