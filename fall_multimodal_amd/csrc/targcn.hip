@@ -19,6 +19,7 @@
 #include "targcn.h"
 
 #include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <type_traits>
 
@@ -2860,7 +2861,15 @@ static int gn_resident(const void* kernel) {
 // residency is the same (the occupancy check above is what the cooperative launch adds), the
 // cooperative launch costs 15-20 us of queue latency per call, and a process that used it died with
 // SIGSEGV in rocprofiler-sdk's exit handlers under rocprofv3.
+// F3_GN_NODE=0 (test switch, read per call: the tests compare both forms) turns the node-partitioned
+// form off before anything is enqueued; unset or any other value changes nothing.
+static bool gn_node_off() {
+  const char* env = getenv("F3_GN_NODE");
+  return env && std::strcmp(env, "0") == 0;
+}
+
 static bool gru_fwd_node(const GruFwdArgs& a, hipStream_t s) {
+  if (gn_node_off()) return false;
   const int NG = (a.B + GN_BT - 1) / GN_BT;
   if (!a.hx || !a.rhx || !a.gsync || NG > GN_MAXG || a.V > VMAX || a.prof) return false;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2883,6 +2892,7 @@ int f3_tg_gru_fwd(const GruFwdArgs* a, int b16, hipStream_t s) {
 }
 
 static bool gru_bwd_node(const GruBwdArgs& a, hipStream_t s) {
+  if (gn_node_off()) return false;
   const int NG = (a.B + GN_BT - 1) / GN_BT;
   if (!a.gx1 || !a.gx2 || !a.gsync || NG > GN_MAXG || a.V > VMAX || a.prof) return false;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
