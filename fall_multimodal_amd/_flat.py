@@ -162,9 +162,11 @@ class FlatModule(nn.Module):
 class _SideStep:
     """Fused training step of a side model: forward -> soft-target CE -> backward -> RMSprop on one HIP
     stream, every buffer preallocated. A subclass gives the constructor defaults and, in its
-    forward_backward, the model's extra forward arguments (`_run`)."""
+    forward_backward, the model's extra forward arguments (`_run`). `class_weight`
+    (torch.nn.CrossEntropyLoss(weight=w); train.check_class_weight): the loss launch is f3_soft_ce_w on the
+    [N,C] label, torch's rule for probability targets (the weighted sum divided by N); None: f3_soft_ce."""
 
-    def __init__(self, model, batch, lr, alpha, eps):
+    def __init__(self, model, batch, lr, alpha, eps, class_weight=None):
         self.model, self.N = model, batch
         self.lr, self.alpha, self.eps = lr, alpha, eps
         dev = model.flat_parameters().device
@@ -175,6 +177,10 @@ class _SideStep:
         self.out = torch.empty(batch, model.n_class, dtype=torch.float32, device=dev)
         self.dout = torch.empty_like(self.out)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.class_weight = None
+        if class_weight is not None:
+            from .train import check_class_weight
+            self.class_weight = torch.from_numpy(check_class_weight(class_weight, model.n_class)).to(dev)
         grad_views(model, self.grads, self._grad_is_none)
 
     def _grad_is_none(self, name):
@@ -193,8 +199,12 @@ class _SideStep:
         """Training forward (with the model's extra arguments), loss and backward on the current stream."""
         m, st = self.model, stream_handle()
         m.native_forward(x, self.out, self.ws, *forward_args, stream=st)
-        check(lib().f3_soft_ce(ptr(self.out), ptr(label), self.N, m.n_class, ptr(self.loss), ptr(self.dout), st),
-              "soft ce")
+        if self.class_weight is not None:
+            check(lib().f3_soft_ce_w(ptr(self.out), ptr(label), None, ptr(self.class_weight), self.N, m.n_class, 0.0,
+                                     ptr(self.loss), ptr(self.dout), st), "weighted soft ce")
+        else:
+            check(lib().f3_soft_ce(ptr(self.out), ptr(label), self.N, m.n_class, ptr(self.loss), ptr(self.dout), st),
+                  "soft ce")
         m.native_backward(self.N, self.dout, self.grads, self.ws, st)
 
     def __call__(self, x, label, *draws, **kwdraws):

@@ -35,7 +35,7 @@ EXPORTS = (
     "f3_dwconv_t_forward", "f3_pointwise_conv", "f3_rgb_scratch_floats", "f3_rgb_forward", "f3_rgb_backward",
     "f3_optim_scalars_bytes", "f3_optim_step", "f3_optim_step_ranges", "f3_net_backward_optim", "f3_net_entry_nograd",
     "f3_metrics_bytes", "f3_metrics_reset", "f3_metrics_update", "f3_segment_norms_scratch_bytes", "f3_segment_norms",
-    "f3_soft_ce_ex", "f3_net_loss_ex", "f3_grad_accumulate",
+    "f3_soft_ce_ex", "f3_net_loss_ex", "f3_grad_accumulate", "f3_soft_ce_w", "f3_net_loss_w",
     "f3_optim_hyper_bytes", "f3_optim_hyper_set", "f3_optim_step_hyper", "f3_optim_guard_offset",
     "f3_ema_state_bytes", "f3_ema_set_decay", "f3_ema_update",
 )
@@ -123,6 +123,8 @@ def lib():
         "f3_segment_norms": (I, [P, P, P, I, P, P, I64, ctypes.c_double, P]),
         "f3_soft_ce_ex": (I, [P, P, P, I, I, F, P, P, P]),
         "f3_net_loss_ex": (I, [P, I, P, P, F, P, P, P]),
+        "f3_soft_ce_w": (I, [P, P, P, P, I, I, F, P, P, P]),
+        "f3_net_loss_w": (I, [P, I, P, P, P, F, P, P, P]),
         "f3_grad_accumulate": (I, [P, P, I64, P, P]),
         "f3_ema_state_bytes": (I64, []),
         "f3_ema_set_decay": (I, [P, ctypes.c_double, P]),

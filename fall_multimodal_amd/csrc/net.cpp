@@ -1697,6 +1697,12 @@ int f3_net_loss_ex(f3_net* net, int N, const float* out, const float* label, flo
   return f3_soft_ce_ex(out, label, nullptr, N, net->cfg.num_class, label_smoothing, loss, dout, stream);
 }
 
+int f3_net_loss_w(f3_net* net, int N, const float* out, const float* label, const float* class_weight,
+                  float label_smoothing, float* loss, float* dout, void* stream) {
+  if (!net) return F3_EINVAL;
+  return f3_soft_ce_w(out, label, nullptr, class_weight, N, net->cfg.num_class, label_smoothing, loss, dout, stream);
+}
+
 int f3_net_backward(f3_net* net, int N, const float* params, const float* dout, float* grads, void* workspace,
                     void* stream) {
   return f3_net_backward_phase(net, N, params, dout, grads, workspace, 0, stream);

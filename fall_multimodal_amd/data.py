@@ -64,6 +64,33 @@ def load_windows(paths) -> Windows:
     return Windows(videos, np.concatenate(feats), np.concatenate(sens), np.concatenate(labs))
 
 
+def class_weights(labels, num_class=None, scheme="balanced"):
+    """Per-class loss weights for an imbalanced label set (TrainStep(class_weight=...), the eval loops):
+    `labels` is [N,C] (soft or one-hot, reduced by argmax) or [N] class indices; num_class defaults to C,
+    or to the largest index + 1. "balanced" is N / (C * count_c), sklearn's
+    compute_class_weight("balanced", ...); a class without a sample gets 0.0 (sklearn's division gives inf,
+    which the step's check refuses). Returns float32 [C]; any other scheme raises ValueError."""
+    if scheme != "balanced":
+        raise ValueError(f"class_weights: unknown scheme {scheme!r} (only 'balanced')")
+    y = labels.detach().cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels)
+    if y.ndim == 2:
+        num_class = y.shape[1] if num_class is None else int(num_class)
+        if y.shape[1] != num_class:
+            raise ValueError(f"class_weights: labels have {y.shape[1]} columns, num_class is {num_class}")
+        y = y.argmax(1)
+    elif y.ndim != 1:
+        raise ValueError(f"class_weights: labels must be [N,C] or [N], got shape {y.shape}")
+    y = y.astype(np.int64)
+    if y.size == 0:
+        raise ValueError("class_weights: no labels")
+    num_class = int(y.max()) + 1 if num_class is None else int(num_class)
+    if y.min() < 0 or y.max() >= num_class:
+        raise ValueError(f"class_weights: a label lies outside [0, {num_class})")
+    count = np.bincount(y, minlength=num_class).astype(np.float64)
+    w = np.where(count > 0, y.size / (num_class * np.maximum(count, 1.0)), 0.0)
+    return w.astype(np.float32)
+
+
 def video_split(w: Windows, seed: int = 42):
     """Train / valid / test by unique video name, 60 / 20 / 20 (model/dataloader.py:204-220):
     train_test_split(unique, test_size=0.4) then split the rest 50/50, both shuffled with

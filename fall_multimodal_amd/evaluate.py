@@ -98,28 +98,41 @@ def test(model, loader, loss_fn=None, top_k=(1, 5), num_classes: int | None = No
     return res
 
 
-def _device_pass(model, loader, top_k, label_smoothing=0.0):
+def _device_pass(model, loader, top_k, label_smoothing=0.0, class_weight=None):
     """One eval-mode pass whose loss, top-k and confusion counts stay on the device
     (metrics.StepMetrics, loss computed by the update itself): nothing is concatenated, no
     per-batch .item(); the one copy to the host is result()'s. label_smoothing > 0: the batch loss
     is the smoothed one (f3_soft_ce_ex without a gradient: the reference's one loss_fn also serves
     valid() and test(), model/main.py:175, 226, 280), handed to the update; ranks and confusion
-    counts still come from the unsmoothed label."""
+    counts still come from the unsmoothed label. class_weight (CrossEntropyLoss(weight=w); uploaded
+    once): the batch loss is f3_soft_ce_w's, whatever label_smoothing is; 2-D labels take torch's
+    rule for probability targets (divided by N), 1-D labels its rule for class indices (divided by
+    the sum of the rows' weights, what loss_fn(pred, label) computes for them)."""
     from ._lib import check, lib, ptr, stream_handle
     from .metrics import StepMetrics
-    from .train import check_step_args
+    from .train import check_class_weight, check_step_args
     eps, _ = check_step_args(label_smoothing, 1)
     was_training = model.training
     model.eval()
-    acc = loss = None
+    acc = loss = weight = None
     try:
         for skel, sensor, label in loader:
             out = model(skel, sensor)
             if acc is None:
                 acc = StepMetrics(out.shape[1], top_k, device=out.device)
+                if class_weight is not None:
+                    weight = torch.from_numpy(check_class_weight(class_weight, out.shape[1])).to(out.device)
             label = label.to(out.device)
             label = (label.long() if label.dim() == 1 else label.float()).contiguous()
-            if eps > 0.0:
+            if weight is not None:
+                if loss is None:
+                    loss = torch.zeros(1, dtype=torch.float32, device=out.device)
+                out = out.contiguous()
+                soft, idx = (label, None) if label.dim() == 2 else (None, label)
+                check(lib().f3_soft_ce_w(ptr(out), ptr(soft), ptr(idx), ptr(weight), out.shape[0], out.shape[1], eps,
+                                         ptr(loss), None, stream_handle(out.device)), "fall3 weighted eval loss")
+                acc.update(out, label, loss)
+            elif eps > 0.0:
                 if loss is None:
                     loss = torch.zeros(1, dtype=torch.float32, device=out.device)
                 out = out.contiguous()
@@ -138,20 +151,24 @@ def _device_pass(model, loader, top_k, label_smoothing=0.0):
 
 
 @torch.no_grad()
-def valid_device(model, loader, top_k=(1, 5), label_smoothing=0.0):
+def valid_device(model, loader, top_k=(1, 5), label_smoothing=0.0, class_weight=None):
     """valid() (model/main.py:148-197) with the metrics accumulated on the device: the same mean of
     per-batch mean losses (soft-target CE of the module output, smoothed by `label_smoothing` as
-    CrossEntropyLoss(label_smoothing=...) smooths it) and top-k over all rows."""
-    res = _device_pass(model, loader, top_k, label_smoothing)
+    CrossEntropyLoss(label_smoothing=...) smooths it) and top-k over all rows. `class_weight`
+    (CrossEntropyLoss(weight=w); train.check_class_weight): every batch loss is torch's weighted one, by
+    its rule for probability targets when the loader gives [N,C] labels (divided by N) and by its rule for
+    class indices when it gives [N] labels (divided by the sum of the rows' weights; an index outside
+    [0,C) is an ignored row). A TrainStep with the same weights always applies the first rule."""
+    res = _device_pass(model, loader, top_k, label_smoothing, class_weight)
     return {"loss": res["loss"], "top_k": res["top_k"]}
 
 
 @torch.no_grad()
-def test_device(model, loader, top_k=(1, 5), label_smoothing=0.0):
+def test_device(model, loader, top_k=(1, 5), label_smoothing=0.0, class_weight=None):
     """test() (model/main.py:199-245, main_cross_validation.py:247) with the metrics accumulated on the
-    device: the keys and values of test() except the sklearn text `report`; `label_smoothing` as in
-    valid_device."""
-    res = _device_pass(model, loader, top_k, label_smoothing)
+    device: the keys and values of test() except the sklearn text `report`; `label_smoothing` and
+    `class_weight` as in valid_device."""
+    res = _device_pass(model, loader, top_k, label_smoothing, class_weight)
     return {k: res[k] for k in ("loss", "top_k", "precision", "recall", "f1", "specificity", "confusion")}
 
 

@@ -170,8 +170,8 @@ class MusaStep(_SideStep):
     """Fused musa_model training step: forward -> soft-target CE -> backward -> RMSprop on one HIP
     stream with preallocated buffers (main.py's train loop body with RMSprop(lr=1e-3))."""
 
-    def __init__(self, model: Model, batch, lr=1e-3, alpha=0.99, eps=1e-8):
-        super().__init__(model, batch, lr, alpha, eps)
+    def __init__(self, model: Model, batch, lr=1e-3, alpha=0.99, eps=1e-8, class_weight=None):
+        super().__init__(model, batch, lr, alpha, eps, class_weight)
         self.last_seed = None
 
     def _grad_is_none(self, name):

@@ -148,8 +148,8 @@ class SktrStep(_SideStep):
     """Fused SkeletonTransformer training step: forward -> soft-target CE -> backward -> RMSprop on
     one HIP stream, every buffer preallocated (the CV notebook's loop body for one fold)."""
 
-    def __init__(self, model: SkeletonTransformer, batch, lr=1e-3, alpha=0.99, eps=1e-8):
-        super().__init__(model, batch, lr, alpha, eps)
+    def __init__(self, model: SkeletonTransformer, batch, lr=1e-3, alpha=0.99, eps=1e-8, class_weight=None):
+        super().__init__(model, batch, lr, alpha, eps, class_weight)
         self.last_draws = None
 
     def forward_backward(self, x, label, sd=None, seed=None):

@@ -115,8 +115,8 @@ class TargcnStep(_SideStep):
     stream, every buffer preallocated (the notebook's loop body, TARGCN_HAR_conv_10kfold.ipynb
     cell 3, with its RMSprop(lr=1e-5))."""
 
-    def __init__(self, model: TARGCN, batch, lr=1e-5, alpha=0.99, eps=1e-8):
-        super().__init__(model, batch, lr, alpha, eps)
+    def __init__(self, model: TARGCN, batch, lr=1e-5, alpha=0.99, eps=1e-8, class_weight=None):
+        super().__init__(model, batch, lr, alpha, eps, class_weight)
 
     def forward_backward(self, source, label):
         self._check(source, label)

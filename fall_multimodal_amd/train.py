@@ -107,6 +107,32 @@ def check_step_args(label_smoothing=0.0, accum_iter=1):
     return float(label_smoothing), int(accum_iter)
 
 
+def check_class_weight(w, num_class):
+    """TrainStep's check of its class weights (no device needed): a sequence, ndarray or tensor of exactly
+    `num_class` real numbers, each finite and >= 0 and not all zero (torch.nn.CrossEntropyLoss(weight=w)
+    with a weight it can divide by). Returns a float32 ndarray [num_class]; anything else raises ValueError."""
+    if isinstance(w, torch.Tensor):
+        w = w.detach().cpu().numpy()
+    if isinstance(w, (str, bytes)) or w is None:
+        raise ValueError(f"class_weight must be {num_class} real numbers, got {w!r}")
+    try:
+        a = np.asarray(w)
+    except Exception as e:  # a ragged sequence
+        raise ValueError(f"class_weight must be {num_class} real numbers, got {w!r}") from e
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.floating)):
+        raise ValueError(f"class_weight must be {num_class} real numbers, got dtype {a.dtype}")
+    if a.shape != (int(num_class),):
+        raise ValueError(f"class_weight must have shape ({int(num_class)},), got {a.shape}")
+    a = a.astype(np.float64)
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError(f"class_weight must be finite and >= 0, got {a.tolist()}")
+    with np.errstate(over="ignore"):
+        a32 = a.astype(np.float32)
+    if not np.isfinite(a32).all() or not (a32 > 0).any():
+        raise ValueError(f"class_weight must be finite in float32 and not all zero, got {a.tolist()}")
+    return a32
+
+
 def check_ema_decay(ema_decay):
     """TrainStep's check of its averaging setting (no device needed): a number in [0, 1], the range in which
     get_ema_multi_avg_fn's lerp stays between the average and the parameters. Returns the float."""
@@ -166,6 +192,21 @@ class TrainStep:
     smoothed loss), ranks and confusion counts come from the unsmoothed label. At 0.0 (the default) the
     step issues f3_net_loss as ever.
 
+    `class_weight` (torch.nn.CrossEntropyLoss(weight=w), the usual first remedy for an imbalanced label set;
+    data.class_weights gives sklearn's "balanced" ones): `num_class` finite numbers >= 0, not all zero
+    (check_class_weight), kept in a device f32[C] tensor. The loss launch is then f3_net_loss_w, with
+    `label_smoothing` as given, 0 included; `loss`, `dout` and the metrics' loss are the weighted ones, ranks
+    and confusion counts are unchanged. prepare() turns 1-D labels into one-hot rows as the reference's loop
+    does (model/main.py:104-113), so the step ALWAYS applies torch's rule for probability targets: the sum of
+    w_c y'_c lsm_c over the batch divided by N. With non-uniform weights that is not what torch computes for
+    class-index targets, which divides by the sum of the rows' weights instead (evaluate.valid_device with
+    1-D labels is the one path that applies that rule). The divisor is N on every rank, so data parallelism
+    and accum_iter need nothing new. `step.class_weight` returns a copy; setting it validates the value and
+    copies it into the device tensor in place (eager, never inside a capture): the launch reads the weights
+    when it runs, so a captured step follows the change on its next replay. Setting it on a step built with
+    None, or to None, raises ValueError (the graph holds another launch). None (the default): no buffer and
+    exactly the launches the step always issued.
+
     `accum_iter` (TRAIN.ACCUM_ITER, model/main.py:115-132): above 1 every call runs forward, loss and the
     whole backward into `grads`, then adds `grads` into the flat `accum` (f3_grad_accumulate; the first
     micro-batch after an update overwrites), and only update calls all-reduce `accum` and run the flat
@@ -209,7 +250,7 @@ class TrainStep:
 
     def __init__(self, model, batch, lr=1e-3, alpha=0.99, eps=1e-8, process_group=None, optimizer=None,
                  phased=None, force_sync=False, max_norm=None, metrics=None, label_smoothing=0.0, accum_iter=1,
-                 ema_decay=None, skip_nonfinite=False):
+                 ema_decay=None, class_weight=None, skip_nonfinite=False):
         if not isinstance(skip_nonfinite, bool):
             raise ValueError(f"TrainStep: skip_nonfinite must be True or False, got {skip_nonfinite!r}")
         self._skip_nonfinite = skip_nonfinite
@@ -262,6 +303,10 @@ class TrainStep:
         self.out = torch.empty(batch, model.spec.num_class, dtype=torch.float32, device=dev)
         self.dout = torch.empty_like(self.out)
         self.loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        # the class weights (class_weight): a device f32[C] tensor the loss launch reads when it runs
+        self._class_weight = None
+        if class_weight is not None:
+            self._class_weight = torch.from_numpy(check_class_weight(class_weight, model.spec.num_class)).to(dev)
         if metrics is True:
             metrics = _metrics.StepMetrics(model.spec.num_class, top_k=(1,), device=dev)
         if metrics is not None and (not isinstance(metrics, _metrics.StepMetrics)
@@ -340,7 +385,10 @@ class TrainStep:
         st = stream_handle()
         m = self.model
         m.native_forward(skel, sensor, self.out, self.ws, True, st)
-        if self.label_smoothing > 0.0:
+        if self._class_weight is not None:
+            check(L.f3_net_loss_w(m._native.h, self.N, ptr(self.out), ptr(label), ptr(self._class_weight),
+                                  self.label_smoothing, ptr(self.loss), ptr(self.dout), st), "fall3 weighted loss")
+        elif self.label_smoothing > 0.0:
             check(L.f3_net_loss_ex(m._native.h, self.N, ptr(self.out), ptr(label), self.label_smoothing,
                                    ptr(self.loss), ptr(self.dout), st), "fall3 smoothed loss")
         else:
@@ -370,6 +418,23 @@ class TrainStep:
     def skip_nonfinite(self):
         """Whether the step skips an update on a non-finite gradient: fixed at construction."""
         return self._skip_nonfinite
+
+    @property
+    def class_weight(self):
+        """A copy of the class weights in force (None: the step's loss is unweighted). Setting them validates
+        the value (check_class_weight) and copies it into the device tensor in place, eagerly: the next step
+        follows it, replayed ones included."""
+        return None if self._class_weight is None else self._class_weight.clone()
+
+    @class_weight.setter
+    def class_weight(self, value):
+        if self._class_weight is None or value is None:
+            raise ValueError("TrainStep: class_weight can be changed only on a step built with class weights, and "
+                             "not to None (the step, and a captured graph, hold another loss launch)")
+        w = check_class_weight(value, self.model.spec.num_class)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("TrainStep: the class weights are written eagerly, never inside a capture")
+        self._class_weight.copy_(torch.from_numpy(w))
 
     def _legacy(self, group):
         """Plain RMSprop (no decay, no clipping, no guard): the launches of f3_rmsprop_step /

@@ -21,6 +21,7 @@
  *                         134-135, 189-200 (accumulated on the device: no copy or sync per batch)
  *   f3_segment_norms   <- param.grad.norm().item() per parameter   model/main.py:84-89
  *   f3_net_loss_ex     <- CrossEntropyLoss(label_smoothing=TRAIN.LABEL_SMOOTHING)   model/main.py:280
+ *   f3_net_loss_w      <- CrossEntropyLoss(weight=w, label_smoothing=eps): per-class weights
  *   f3_grad_accumulate <- .grad += g between the optimizer steps of TRAIN.ACCUM_ITER  model/main.py:115-132
  *   f3_ema_update      <- AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(decay)).update_parameters(model)
  *                         after optimizer.step() (torch.optim.swa_utils; the loop itself has no averaging)
@@ -349,6 +350,41 @@ int f3_soft_ce_ex(const float* out, const float* label, const int64_t* label_idx
 /* f3_net_loss with smoothing: f3_soft_ce_ex(out, label, NULL, batch, num_class, ...). */
 int f3_net_loss_ex(f3_net* net, int batch, const float* out, const float* label, float label_smoothing,
                    float* loss, float* dout, void* stream);
+/* f3_soft_ce_w / f3_net_loss_w  <- torch.nn.CrossEntropyLoss(weight=w, label_smoothing=eps)(pred, label), the
+ *                                  usual first remedy for an imbalanced label set (the fall classes are a
+ *                                  small share of UP-Fall's windows); one loss_fn for train, valid and test
+ * class_weight: device f32[C], w_c >= 0 and finite (checked by the caller, not here). The launch reads it
+ * when it runs: a call recorded into a HIP graph follows a later in-place change of the array. With
+ * lsm = log_softmax(out) torch has two normalisations, and the label form picks one:
+ *   label (f32[N,C], soft or one-hot): the probability rule
+ *     y'   = y (1 - eps) + eps / C
+ *     a_nc = w_c y'_nc                  m_n = sum_c a_nc
+ *     loss = -(1/N) sum_n sum_c a_nc lsm_nc
+ *     dout = (softmax(out)_nc m_n - a_nc) / N                    (rows are not renormalised)
+ *   label_idx (i64[N]): the index rule. A row is live when 0 <= t_n < C; every other index is torch's
+ *   ignore_index row. Sums run over live rows only:
+ *     a_nc = (1 - eps) w_c [c == t_n] + (eps / C) w_c
+ *     W    = sum over live n of w_{t_n}
+ *     loss = -(1/W) sum_n sum_c a_nc lsm_nc
+ *     dout = (softmax(out)_nc m_n - a_nc) / W                    (an ignored row's dout is 0)
+ *   W == 0 (no live row, or only rows of weight 0) gives a NaN loss and an all-NaN dout, as torch's 0/0.
+ * The row is f3_soft_ce_ex's with a = y' * w (rounded on its own, after y') in the place of y' and m in
+ * the place of sum_c y'_c: the same sequential fp32 sums in the same order, the register path up to
+ * C = 16 and the row-in-memory path beyond. So all-ones weights give f3_soft_ce_ex's bits under either
+ * rule (all indices in range), and weights that are all 2 give twice them (probability rule) or exactly
+ * them (index rule, W = 2N). W is accumulated in fp64 in a fixed order and rounded to fp32 once: summed
+ * in fp32 its error alone left the dout gate of the tests at N = 257. N <= 4096: one launch, for index
+ * labels with a pre-pass over the labels for W. Larger N: up to 1024 workgroups store one partial each
+ * into a block the library owns and a second launch adds them in index order; for index labels a
+ * launch before them stores the fp64 partials of W, which every workgroup then adds in one fixed
+ * order. Such calls must not overlap on two streams. dout == NULL: the loss word only. No float
+ * atomics, no allocation, no sync; the same inputs give the same bits. F3_EINVAL: everything
+ * f3_soft_ce_ex refuses, and a null class_weight. */
+int f3_soft_ce_w(const float* out, const float* label, const int64_t* label_idx, const float* class_weight, int N,
+                 int C, float label_smoothing, float* loss, float* dout, void* stream);
+/* f3_net_loss_ex with class weights: f3_soft_ce_w(out, label, NULL, class_weight, batch, num_class, ...). */
+int f3_net_loss_w(f3_net* net, int batch, const float* out, const float* label, const float* class_weight,
+                  float label_smoothing, float* loss, float* dout, void* stream);
 /* One micro-batch's gradient into the accumulator: every thread reads the device word *reset_flag;
  * non-zero (the first micro-batch after model.zero_grad(), main.py:132): acc[i] = grads[i], bit for
  * bit; zero: acc[i] = acc[i] + grads[i], one fp32 add per element, the order in which autograd's
